@@ -1,26 +1,40 @@
 #!/usr/bin/env python3
 """Benchmark of the GeoA3 inner attack loop on MI355X (BASELINE.json metric: attack-iterations/sec at B=250).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is ONE inner iteration of the attack (Attacker/geoA3_attack.py:238-352) applied to every victim instance
 held by a GPU: success check + victim forward + CE/CD/HD/curvature objective + input gradient + Adam step.
 
+A plain run sets up, runs the untimed iterations, times exactly K steps and prints ONE short JSON line: the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and the description of the workload.  No event
+timers run in its timed window.  `--full` adds everything else the benchmark measures: per-kernel times (HIP events
+inside the timed window and extra iterations after it), rooflines, the host enqueue cost, the vector-only 1-NN search,
+the strict fp32-MFMA run, the shard proxy's full-batch comparison, `multi_gpu`, `other_configs` and the CPU baseline.
+`--no-cpu-baseline`, `--single-mode`, `--no-proxy-full` and `--no-other-configs` take parts out of a `--full` run.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (float32, or
+float64 for integer arrays): the iterate `x` the next step starts from, the victim's `logits`, the two gradient parts
+`g_cls` / `g_geo`, the losses (`loss_n`, `cls_loss`, `dis_loss`, `hd_loss`, `curv_loss`, `constrain`) and the running
+result (`best_attack`, `best_loss`, `best_step`), all with the instances on axis 0 (the ranks' rows concatenated in rank
+order).  Above 64 MB in all, a fixed seeded sample of the instances is written.  The inputs are seeded, so two runs with
+the same arguments compute from the same inputs.
+
 Workloads (BASELINE.json `configs`):
   default                         configs[1]: PointNet, 1024 points, 250 instances, full GeoA3 (CD 1.0 + HD 0.1 + curvature
                                   1.0 with k=16), untargeted CE -- the configuration the metric is quoted on.  The
                                   headline keys of the JSON line describe THIS workload and nothing else.
-                                  With no workload flag the same run then appends `other_configs`: configs[3], configs[4],
-                                  the 32-instance shard of configs[2] (with its full-batch comparison) and configs[1] /
-                                  configs[4] / configs[3] on CAD-like clouds -- GPU legs only, `--other-steps` timed steps each
-                                  (`--no-other-configs` skips them)
+                                  With --full and no workload flag the same run then appends `other_configs`: configs[3],
+                                  configs[4], the 32-instance shard of configs[2] (with its full-batch comparison) and
+                                  configs[1] / configs[4] / configs[3] on CAD-like clouds -- GPU legs only, `--other-steps`
+                                  timed steps each (`--no-other-configs` skips them)
   --gpus N (N > 1)                configs[2]: the SAME 250-instance batch sharded over N GPUs (`--scaling strong`, the
                                   default: rank r holds shard_bounds(250, N)[r] instances, loss divisor 1/250, no
                                   collective in the iteration); `--scaling weak` holds 250 instances on EVERY GPU.
-                                  The line also carries `multi_gpu`: the OTHER scaling mode measured briefly, per-rank
-                                  ms/step, the result gather of the batch over the process group, and an all-gather of
-                                  the rank ids
+                                  With --full the line also carries `multi_gpu`: the OTHER scaling mode measured briefly,
+                                  per-rank ms/step, the result gather of the batch over the process group, and an
+                                  all-gather of the rank ids
   --instances 32                  1-GPU proxy of configs[2]: one rank's shard of the 8-way split (global divisor 250)
   --arch PointNetPP               configs[3]: PointNet++ SSG victim
   --npoint 4096 --knn 32          configs[4]
@@ -38,6 +52,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
@@ -368,11 +384,14 @@ class Bench:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
         return float(t.item())
 
-    def measure(self, arch, pts, npoint, knn, global_batch, wide_mode, steps, warmup, presteps, timed_tags):
+    def measure(self, arch, pts, npoint, knn, global_batch, wide_mode, steps, warmup, presteps, timed_tags, full=True,
+                outputs=False):
         """`presteps` + `warmup` untimed, then exactly `steps` timed inner iterations between two barriers
-        -> dict(dt = seconds, max over ranks; dt_local; kms = per-kernel average ms by event-timer tag; extra;
-        host_enqueue_ms = cost of ENQUEUEING one iteration into an empty queue; host_loop_ms = host time per step inside the
-        timed loop, which includes blocking on a full queue)."""
+        -> dict(dt = seconds, max over ranks; dt_local; host_loop_ms = host time per step inside the timed loop, which
+        includes blocking on a full queue; outputs = step_outputs() of the last timed step when `outputs`).
+        full: HIP events around `timed_tags` inside the timed window, then extra untimed iterations for kms = per-kernel
+        average ms by event-timer tag, extra, host_enqueue_ms = cost of ENQUEUEING one iteration into an empty queue and
+        nn1_vector_only_us; without it the timed window runs alone and nothing runs after it."""
         torch, lib = self.torch, self.lib
         from geoa3_amd.attack import AttackRunner
         ori, nrm, gt = pts
@@ -396,8 +415,9 @@ class Bench:
         mask = 0
         for t in timed_tags:
             mask |= 1 << t
-        lib.geoa3_profile_enable(steps)
-        lib.geoa3_profile_select(mask)
+        if full:
+            lib.geoa3_profile_enable(steps)
+            lib.geoa3_profile_select(mask)
         t0 = time.perf_counter()
         for s in range(presteps + warmup, total):
             runner.step(s, 0)
@@ -405,6 +425,13 @@ class Bench:
         self.barrier()
         dt_local = time.perf_counter() - t0
         dt = self.max_over_ranks(dt_local)
+        res = {"dt": dt, "dt_local": dt_local, "host_loop_ms": host_loop / steps * 1e3}
+        if outputs:
+            res["outputs"] = step_outputs(runner)
+        if not full:
+            runner.end_search_step()
+            del runner
+            return res
 
         def kernel_ms(tag):
             buf = (C.c_float * steps)()
@@ -461,8 +488,40 @@ class Bench:
                         raise RuntimeError("the vector-only 1-NN search and the shipped one disagree")
         runner.end_search_step()
         del runner
-        return {"dt": dt, "dt_local": dt_local, "kms": kms, "extra": n_extra, "host_enqueue_ms": host / n_host * 1e3,
-                "host_loop_ms": host_loop / steps * 1e3, "nn1_vector_only_us": vec_us}
+        res.update(kms=kms, extra=n_extra, host_enqueue_ms=host / n_host * 1e3, nn1_vector_only_us=vec_us)
+        return res
+
+
+def step_outputs(runner):
+    """What the timed path hands its caller after its last step, copied to the host: float32 arrays as they are,
+    integer arrays as float64 (exact).  Every array holds the instances on axis 0."""
+    t, g = runner.t, runner.geo_out
+    arrays = {"x": t["x"], "logits": t["logits"], "g_cls": t["g_cls"], "g_geo": t["g_geo"], "loss_n": t["loss_n"],
+              "cls_loss": t["cls_loss"], "dis_loss": g["dis_loss"], "hd_loss": g["hd_loss"], "curv_loss": g["curv_loss"],
+              "constrain": g["constrain"], "best_attack": t["best_attack"], "best_loss": t["best_loss"],
+              "best_step": t["best_step"]}
+    out = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy()
+        out[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    return out
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, arrays):
+    """arrays -> dirname/<name>.npy; above DUMP_LIMIT_BYTES in all, the same fixed seeded sample of rows (instances) of
+    every array, in their original order."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_LIMIT_BYTES:
+        b = next(iter(arrays.values())).shape[0]
+        keep = max(1, b * DUMP_LIMIT_BYTES // total)
+        rows = np.sort(np.random.default_rng(0).choice(b, keep, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a if rows is None else a[rows])
 
 
 def kernels_ms_dict(kms, extra, timed_tags):
@@ -540,6 +599,11 @@ def main():
     ap.add_argument("--global-batch", type=int, default=BATCH, help="instances of the whole job (strong scaling)")
     ap.add_argument("--instances", type=int, default=0,
                     help="instances held by EACH GPU (overrides the split): 32 = one rank's shard of the 8-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel times, rooflines, the fp32-MFMA run, the shard "
+                         "proxy's comparison, multi_gpu, other_configs, the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-proxy-full", action="store_true",
                     help="shard proxy (--instances): skip the full 250-instance comparison run (profiling)")
@@ -558,7 +622,7 @@ def main():
     ap.add_argument("--arch", default="PointNet", choices=["PointNet", "PointNetPP"],
                     help="victim (PointNetPP = configs[3]: SSG classifier)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default run: only the configs[1] headline, not the `other_configs` legs")
+                    help="the default --full run: only the configs[1] headline, not the `other_configs` legs")
     ap.add_argument("--other-steps", type=int, default=40, help="timed steps of each `other_configs` leg")
     ap.add_argument("--other-presteps", type=int, default=150, help="untimed iterations in front of each `other_configs` leg")
     a = ap.parse_args()
@@ -603,11 +667,19 @@ def main():
     pts = rank_clouds(B, lo, global_batch, mode)
     timed_tags = [TAG_CONV5] if a.arch == "PointNet" else [TAG_SA1_BWD, TAG_SA2_FWD, TAG_SA2_BWD]
     wmode = default_wide_mode() if a.arch == "PointNet" else None
-    m = bench.measure(a.arch, pts, npoint, knn, global_batch, wmode, a.steps, a.warmup, a.presteps, timed_tags)
-    dt, kms, extra = m["dt"], m["kms"], m["extra"]
+    m = bench.measure(a.arch, pts, npoint, knn, global_batch, wmode, a.steps, a.warmup, a.presteps, timed_tags,
+                      full=a.full, outputs=bool(a.dump_outputs))
+    dt = m["dt"]
+    outputs = m.get("outputs")
+    if outputs is not None and use_dist:     # every rank's rows, in rank order
+        parts = [None] * world
+        dist.all_gather_object(parts, outputs)
+        outputs = {k: np.concatenate([p[k] for p in parts]) for k in outputs}
+    if outputs is not None and rank == 0:
+        dump_outputs(a.dump_outputs, outputs)
 
     other = None
-    if a.arch == "PointNet" and not a.single_mode and mode != "shard-proxy":
+    if a.full and a.arch == "PointNet" and not a.single_mode and mode != "shard-proxy":
         # the same loop with every convolution on the fp32 MFMA (strict fp32 products), shorter, beside the headline
         omode = "f32" if wmode == "f16x2" else "f16x2"
         osteps = max(10, min(a.steps, 40))
@@ -615,7 +687,7 @@ def main():
                            timed_tags)
         other = (omode, osteps, om["dt"], om["kms"])
     proxy = None
-    if mode == "shard-proxy" and a.arch == "PointNet" and not a.no_proxy_full:
+    if a.full and mode == "shard-proxy" and a.arch == "PointNet" and not a.no_proxy_full:
         fpts = bench.clouds(a.arch, gen, npoint, BATCH, seed=100)
         fsteps = max(10, min(a.steps, 60))
         fm = bench.measure(a.arch, fpts, npoint, knn, BATCH, wmode, fsteps, 5, a.presteps, timed_tags)
@@ -623,12 +695,12 @@ def main():
         del fpts
 
     multi = None
-    if use_dist and a.instances == 0:
+    if a.full and use_dist and a.instances == 0:
         multi = multi_gpu_report(bench, a, split, rank_clouds, timed_tags, wmode, m, mode)
 
     # the default command (no workload flag): the other BASELINE.json configurations under the same clock, GPU legs only
-    default_run = (world == 1 and a.arch == "PointNet" and npoint == NPOINT and knn == KNN and a.data == "ellipsoid" and
-                   a.instances == 0 and a.global_batch == BATCH and not a.no_other_configs)
+    default_run = (a.full and world == 1 and a.arch == "PointNet" and npoint == NPOINT and knn == KNN and
+                   a.data == "ellipsoid" and a.instances == 0 and a.global_batch == BATCH and not a.no_other_configs)
     others = None
     if default_run:
         del pts
@@ -661,11 +733,11 @@ def main():
             "metric": "attack-iterations/sec (B=250, N=%d)" % npoint, "value": round(value, 3),
             "unit": "iterations/s of a 250-instance batch", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(ms_per_step, 4),
-            "host_enqueue_ms_per_step": round(m["host_enqueue_ms"], 4),
+            **({"host_enqueue_ms_per_step": round(m["host_enqueue_ms"], 4)} if a.full else {}),
             "host_loop_ms_per_step": round(m["host_loop_ms"], 4),
-            "host_note": "host_enqueue = host time to enqueue ONE iteration into a drained queue (10 untimed iterations after "
-                         "the timed window); host_loop = host time per step inside the timed loop, which includes blocking "
-                         "on a full queue when the GPU is the bound",
+            **({"host_note": "host_enqueue = host time to enqueue ONE iteration into a drained queue (10 untimed iterations "
+                             "after the timed window); host_loop = host time per step inside the timed loop, which includes "
+                             "blocking on a full queue when the GPU is the bound"} if a.full else {}),
             "higher_is_better": True,
             "ranks_seen": dist.get_world_size() if use_dist else 1,
             "backend": ("rccl (torch.distributed 'nccl')" if backend == "nccl" else backend) if use_dist else None,
@@ -691,46 +763,49 @@ def main():
                        "classes": CLASSES, "wide_mode": wmode, "presteps": a.presteps,
                        "parallelism": "instance-sharded x%d" % world},
         }
-        full_size = B == BATCH and a.data == "ellipsoid"
-        if a.arch == "PointNet":
-            from geoa3_amd.pointnet import wide_shape
-            kn = (("wide16_kernel<3" if wide_shape("conv5") == 16 else "wide_split_kernel<3") if wmode == "f16x2"
-                  else "wide_max2_kernel<3")
-            out["roofline"] = attach_traffic(conv5_roofline(wmode, kms.get(TAG_CONV5), B, npoint), kn,
-                                             "c2" if npoint < 4096 else "c5", full_size and npoint in (1024, 4096))
-            if npoint >= 4096:
-                out["knn_kernel"] = attach_traffic(knn_kernel_line(kms.get(TAG_KNN), B, npoint, knn), "knn_grid_kernel", "c5",
-                                                   full_size)
-        else:
-            roofs = pn2_rooflines(kms, B)
-            big = max(roofs, key=lambda t: roofs[t]["avg_launch_ms"]) if roofs else None
-            out["roofline"] = attach_traffic(roofs.get(big), {TAG_SA1_BWD: "sa1_bwd_kernel", TAG_SA2_FWD: "sa2_fwd8_kernel",
-                                                             TAG_SA2_BWD: "sa2b_bwd_kernel"}.get(big, ""), "c4", full_size)
-            out["other_large_kernels"] = [roofs[t] for t in roofs if t != big]
-        if other is not None:
-            omode, osteps, odt, okms = other
-            oroof = attach_traffic(conv5_roofline(omode, okms.get(TAG_CONV5), B, npoint),
-                                   "wide_max2_kernel<3" if omode == "f32" else "wide16_kernel<3",
-                                   "c2f32" if omode == "f32" else "c2", full_size and npoint == NPOINT)
-            out["other_wide_mode"] = {"wide_mode": omode, "value": round((total_instances * osteps / odt) / BATCH, 3),
-                                      "ms_per_step": round(odt / osteps * 1e3, 4), "steps": osteps,
-                                      "roofline": oroof,
-                                      "kernels_ms": {"conv5_wide_max": okms.get(TAG_CONV5),
-                                                     "tnet_wide_max(x2)": okms.get(TAG_TNET)}}
-        if proxy is not None:
-            fsteps, fdt = proxy
-            out["strong_scaling_proxy"] = proxy_dict(fdt / fsteps * 1e3, ms_per_step, B, global_batch)
-        out["cd_kernel"] = cd_kernel_line(kms.get(TAG_NN1), B, npoint, m.get("nn1_vector_only_us"))
-        out["kernels_ms"] = kernels_ms_dict(kms, extra, timed_tags)
-        if multi is not None:
-            out["multi_gpu"] = multi
-        if others is not None:
-            out["other_configs"] = others
-        if not a.no_cpu_baseline and world == 1:
-            try:
-                out["cpu_baseline"] = cpu_baseline(a.arch, npoint, knn, budget_s=a.cpu_budget, threads=a.cpu_threads)
-            except Exception as e:  # the baseline never blocks the GPU number
-                out["cpu_baseline"] = {"value": None, "error": repr(e)}
+        if a.full:
+            kms, extra = m["kms"], m["extra"]
+            full_size = B == BATCH and a.data == "ellipsoid"
+            if a.arch == "PointNet":
+                from geoa3_amd.pointnet import wide_shape
+                kn = (("wide16_kernel<3" if wide_shape("conv5") == 16 else "wide_split_kernel<3") if wmode == "f16x2"
+                      else "wide_max2_kernel<3")
+                out["roofline"] = attach_traffic(conv5_roofline(wmode, kms.get(TAG_CONV5), B, npoint), kn,
+                                                 "c2" if npoint < 4096 else "c5", full_size and npoint in (1024, 4096))
+                if npoint >= 4096:
+                    out["knn_kernel"] = attach_traffic(knn_kernel_line(kms.get(TAG_KNN), B, npoint, knn), "knn_grid_kernel",
+                                                       "c5", full_size)
+            else:
+                roofs = pn2_rooflines(kms, B)
+                big = max(roofs, key=lambda t: roofs[t]["avg_launch_ms"]) if roofs else None
+                out["roofline"] = attach_traffic(roofs.get(big), {TAG_SA1_BWD: "sa1_bwd_kernel",
+                                                                 TAG_SA2_FWD: "sa2_fwd8_kernel",
+                                                                 TAG_SA2_BWD: "sa2b_bwd_kernel"}.get(big, ""), "c4", full_size)
+                out["other_large_kernels"] = [roofs[t] for t in roofs if t != big]
+            if other is not None:
+                omode, osteps, odt, okms = other
+                oroof = attach_traffic(conv5_roofline(omode, okms.get(TAG_CONV5), B, npoint),
+                                       "wide_max2_kernel<3" if omode == "f32" else "wide16_kernel<3",
+                                       "c2f32" if omode == "f32" else "c2", full_size and npoint == NPOINT)
+                out["other_wide_mode"] = {"wide_mode": omode, "value": round((total_instances * osteps / odt) / BATCH, 3),
+                                          "ms_per_step": round(odt / osteps * 1e3, 4), "steps": osteps,
+                                          "roofline": oroof,
+                                          "kernels_ms": {"conv5_wide_max": okms.get(TAG_CONV5),
+                                                         "tnet_wide_max(x2)": okms.get(TAG_TNET)}}
+            if proxy is not None:
+                fsteps, fdt = proxy
+                out["strong_scaling_proxy"] = proxy_dict(fdt / fsteps * 1e3, ms_per_step, B, global_batch)
+            out["cd_kernel"] = cd_kernel_line(kms.get(TAG_NN1), B, npoint, m.get("nn1_vector_only_us"))
+            out["kernels_ms"] = kernels_ms_dict(kms, extra, timed_tags)
+            if multi is not None:
+                out["multi_gpu"] = multi
+            if others is not None:
+                out["other_configs"] = others
+            if not a.no_cpu_baseline and world == 1:
+                try:
+                    out["cpu_baseline"] = cpu_baseline(a.arch, npoint, knn, budget_s=a.cpu_budget, threads=a.cpu_threads)
+                except Exception as e:  # the baseline never blocks the GPU number
+                    out["cpu_baseline"] = {"value": None, "error": repr(e)}
         print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()

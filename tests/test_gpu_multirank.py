@@ -35,7 +35,7 @@ def _env():
 def test_bench_two_ranks_strong_scaling_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps",
-           "6", "--warmup", "2", "--presteps", "4", "--single-mode", "--no-cpu-baseline"]
+           "6", "--warmup", "2", "--presteps", "4", "--full", "--single-mode", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_env(), cwd=REPO, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -61,14 +61,15 @@ def test_bench_two_ranks_strong_scaling_on_one_gpu():
 
 
 @pytest.mark.timeout(900)
-def test_bench_spawns_its_own_ranks():
+def test_bench_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` WITHOUT a launcher (the way the driver calls `--gpus 1`): the parent must start the two
-    ranks itself (a child torch.distributed.run, before anything touches the GPU) and rank 0's line must say so."""
+    ranks itself (a child torch.distributed.run, before anything touches the GPU) and rank 0's line must say so; the
+    outputs it dumps hold both ranks' rows."""
     env = _env()
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--presteps",
-           "2", "--single-mode", "--no-cpu-baseline"]
+           "2", "--single-mode", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=REPO, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -76,6 +77,7 @@ def test_bench_spawns_its_own_ranks():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["backend"] == "gloo"
     assert out["config"]["instances_per_gpu"] == 125 and out["scaling"] == "strong"
+    assert np.load(os.path.join(tmp_path, "x.npy")).shape == (250, 3, 1024)
 
 
 @pytest.mark.timeout(900)

@@ -7,6 +7,17 @@ import torch
 from oracle import geoa3_oracle as O
 
 T = torch.from_numpy
+FIXTURE_THREADS = 8
+
+
+@pytest.fixture(autouse=True)
+def _fixture_threads():
+    """The fixtures' fp32 convolutions were recorded on 8 intra-op threads, and oneDNN splits a convolution's sums by the
+    thread count: the oracle runs on the same count whatever the host's cores or OMP_NUM_THREADS."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(FIXTURE_THREADS)
+    yield
+    torch.set_num_threads(n)
 
 
 def _close(a, b, rtol=1e-5, atol=1e-7):

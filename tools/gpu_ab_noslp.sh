@@ -6,7 +6,7 @@
 #       python -m geoa3_amd.build --variant geoa3_amd/lib_g3        (round 5: +5.5 % on configs[1]; every other group: 0 to +1 us)
 # then list the libraries to compare in the loop below.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-run() { GEOA3_LIB_PATH=$PWD/$1 python3 bench.py --no-cpu-baseline --single-mode $2 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); k=d.get('kernels_ms') or {}; print('$1 [$2]', d['ms_per_step'], {a: round(b, 4) for a, b in k.items() if isinstance(b, float)})"; }
+run() { GEOA3_LIB_PATH=$PWD/$1 python3 bench.py --full --no-cpu-baseline --single-mode $2 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); k=d.get('kernels_ms') or {}; print('$1 [$2]', d['ms_per_step'], {a: round(b, 4) for a, b in k.items() if isinstance(b, float)})"; }
 for rep in 1 2; do for l in geoa3_amd/lib/libgeoa3_hip.so geoa3_amd/lib_noslp/libgeoa3_hip.so; do
   run $l "--steps 200 --warmup 20"
   run $l "--instances 32 --no-proxy-full --steps 300 --warmup 20"

@@ -7,7 +7,7 @@ pat=$1; shift
 for l in "$@"; do
   d=gpurun_out/kstats_$(echo $l | tr '/.' '__')
   rm -rf $d
-  GEOA3_LIB_PATH=$PWD/$l rocprofv3 --kernel-trace --stats --output-format csv -d $d -o k -- python3 bench.py --no-cpu-baseline --single-mode --steps 100 --warmup 10 > /dev/null 2>&1
+  GEOA3_LIB_PATH=$PWD/$l rocprofv3 --kernel-trace --stats --output-format csv -d $d -o k -- python3 bench.py --full --no-cpu-baseline --single-mode --steps 100 --warmup 10 > /dev/null 2>&1
   echo "== $l"
   f=$(find $d -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$pat" <<'PY'

@@ -2,7 +2,7 @@
 # kernel start / end times of one PointNet++ forward with the side queue on (which kernels overlap)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/pn2tl; rm -rf $O; mkdir -p $O
-GEOA3_GEO_STREAM=0 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o t -- python3 bench.py --no-cpu-baseline --single-mode --arch PointNetPP --steps 6 --warmup 2 --presteps 4 > $O/log.txt 2>&1
+GEOA3_GEO_STREAM=0 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o t -- python3 bench.py --full --no-cpu-baseline --single-mode --arch PointNetPP --steps 6 --warmup 2 --presteps 4 > $O/log.txt 2>&1
 python3 - $O <<'P'
 import csv,sys,glob
 f=glob.glob(sys.argv[1]+'/trace/**/t_kernel_trace.csv', recursive=True)[0]

@@ -5,7 +5,7 @@
 set -x
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/prof}; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --single-mode --no-other-configs"
+B="python3 bench.py --full --no-cpu-baseline --single-mode --no-other-configs"
 # configs[1]
 GEOA3_PN2_SIDE=0 GEOA3_GEO_STREAM=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2/trace -o t -- $B --steps 60 --warmup 10 > $O/c2_trace.log 2>&1
 GEOA3_PN2_SIDE=0 GEOA3_GEO_STREAM=0 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/c2/fetch -o t -- $B --steps 30 --warmup 5 --presteps 100 > $O/c2_fetch.log 2>&1
@@ -33,10 +33,10 @@ python3 tools/trace_timeline.py $O/c5/trace > $O/c5_timeline.txt
 # per-dispatch CSVs are large: keep the statistics and the counter collections only
 find $O -name '*kernel_trace.csv' -delete
 # un-profiled bench lines (both streams, CPU baselines)
-python3 bench.py --steps 200 --warmup 10 > $O/bench_config2.json 2> $O/bench.err
-python3 bench.py --instances 32 --steps 300 --warmup 10 --no-cpu-baseline > $O/bench_proxy32.json 2>> $O/bench.err
-python3 bench.py --arch PointNetPP --steps 40 --warmup 5 --presteps 20 > $O/bench_config4.json 2>> $O/bench.err
-python3 bench.py --npoint 4096 --knn 32 --steps 40 --warmup 5 --presteps 60 > $O/bench_config5.json 2>> $O/bench.err
+python3 bench.py --full --steps 200 --warmup 10 > $O/bench_config2.json 2> $O/bench.err
+python3 bench.py --full --instances 32 --steps 300 --warmup 10 --no-cpu-baseline > $O/bench_proxy32.json 2>> $O/bench.err
+python3 bench.py --full --arch PointNetPP --steps 40 --warmup 5 --presteps 20 > $O/bench_config4.json 2>> $O/bench.err
+python3 bench.py --full --npoint 4096 --knn 32 --steps 40 --warmup 5 --presteps 60 > $O/bench_config5.json 2>> $O/bench.err
 # the whole CLI run of configs[1] (10 binary steps x 500 iterations, 250 instances; synthetic data and weights) in both
 # arithmetic modes: wall time of attack() incl. setup and the result download
 for m in f16x2 f32; do

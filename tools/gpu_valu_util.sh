@@ -3,7 +3,7 @@
 # VALU instructions per wavefront.  bash tools/gpu_valu_util.sh outdir [more bench.py arguments, e.g. --arch PointNetPP]
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/valu}; mkdir -p $O; shift
-B="python3 bench.py --no-cpu-baseline --single-mode --steps 6 --warmup 2 --presteps 100 $*"
+B="python3 bench.py --full --no-cpu-baseline --single-mode --steps 6 --warmup 2 --presteps 100 $*"
 GEOA3_GEO_STREAM=0 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_INSTS_LDS --output-format csv -d $O/a -o t -- $B > $O/a.log 2>&1
 GEOA3_GEO_STREAM=0 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/b -o t -- $B > $O/b.log 2>&1
 GEOA3_GEO_STREAM=0 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_ANY --output-format csv -d $O/c -o t -- $B > $O/c.log 2>&1

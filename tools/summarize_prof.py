@@ -10,11 +10,11 @@ import os
 import shutil
 import sys
 
-TITLES = {"c2": "configs[1]: PointNet 1024-pt, 250 instances (`python3 bench.py --no-cpu-baseline --single-mode`)",
-          "p32": "configs[2] proxy: one rank's 32-instance shard (`bench.py --instances 32 --no-proxy-full`)",
+TITLES = {"c2": "configs[1]: PointNet 1024-pt, 250 instances (`python3 bench.py --full --no-cpu-baseline --single-mode`)",
+          "p32": "configs[2] proxy: one rank's 32-instance shard (`bench.py --full --instances 32 --no-proxy-full`)",
           "c2f32": "configs[1] with GEOA3_WIDE_MODE=f32 (every convolution on the fp32 MFMA: the bench line's `other_wide_mode`)",
-          "c4": "configs[3]: PointNet++ SSG (`bench.py --arch PointNetPP`)",
-          "c5": "configs[4]: PointNet 4096-pt, k=32 (`bench.py --npoint 4096 --knn 32`)"}
+          "c4": "configs[3]: PointNet++ SSG (`bench.py --full --arch PointNetPP`)",
+          "c5": "configs[4]: PointNet 4096-pt, k=32 (`bench.py --full --npoint 4096 --knn 32`)"}
 
 
 def counters(path, name):
