@@ -117,6 +117,10 @@ SIGNATURES = {
     "geoa3_pn2ssg_forward": (C.c_int, [C.POINTER(Pn2SsgWeights), vp, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_pn2ssg_backward": (C.c_int, [C.POINTER(Pn2SsgWeights), vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_fps_sample": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "geoa3_uniform_loss_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "geoa3_uniform_loss": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int, C.c_int,
+                                     vp, vp, vp, vp, vp, vp]),
+    "geoa3_uniform_fold": (C.c_int, [vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp]),
     "geoa3_knn_normal": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_local_frames": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_perp_jitter": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),

@@ -37,11 +37,12 @@ class AttackRunner:
     """Owns the device state of one batch of b attacks in flight and enqueues the loop."""
 
     def __init__(self, net: PointNet, b: int, n: int, cfg, device, global_batch: Optional[int] = None):
-        if _cfg(cfg, "uniform_loss_weight", 0.0) != 0:
-            # the reference's uniform_loss (Lib/loss_utils.py:151-189) calls pointnet2_utils without importing it:
-            # --uniform_loss_weight != 0 dies with a NameError there (geoA3_attack.py:170)
-            raise NotImplementedError("uniform_loss cannot run in the reference either (NameError: pointnet2_utils "
-                                      "is never imported in Lib/loss_utils.py); default weight 0")
+        # --uniform_loss_weight (geoA3_attack.py:168-174): w * U joins every row's constrain loss; U is ONE scalar for the
+        # batch (Lib/loss_utils.py:151-189), so its gradient couples the rows -- a sharded batch would need an all-reduce
+        self.w_uni = float(_cfg(cfg, "uniform_loss_weight", 0.0))
+        if self.w_uni != 0 and global_batch is not None and global_batch != b:
+            raise ValueError("uniform_loss_weight != 0 needs the whole batch on one GPU: U is a mean over all %d "
+                             "instances (this shard holds %d)" % (global_batch, b))
         if cfg.dis_loss_type == "L2" and cfg.hd_loss_weight != 0:
             raise AssertionError("L2 distance needs hd_loss_weight == 0")  # geoA3_attack.py:140
         if cfg.optim not in ("adam", "sgd"):
@@ -153,6 +154,10 @@ class AttackRunner:
         else:
             t["proj_d"], t["proj_i"] = t["d_ao"], t["i_ao"]
         self.geo_out = {name: z(b) for name in ("dis_loss", "hd_loss", "curv_loss", "constrain")}
+        if self.w_uni != 0:   # U [] and dU/dx of the cloud the objective sees (geoa3_uniform_loss)
+            t["uni_loss"], t["uni_grad"] = torch.zeros((), **f32), z(b, 3, ne)
+            self.uni_ws = ops.uniform_workspace(b, ne, device)
+            self.uni_contract = getattr(net, "ext_contract", None)
         self.geo_out["grad"] = t["g_geo"]
         # clouds of 1025..4096 points (or k > 32): the records of the fixed-point objective kernel (geoa3_geo_args.scratch)
         self.geo_scratch = ops.geo_scratch(b, ne, device) if ((1024 < ne or self.k > 32) and ne <= 4096 and self.use_curv) else None
@@ -392,6 +397,12 @@ class AttackRunner:
                                   w_hd=float(cfg.hd_loss_weight), w_curv=float(cfg.curv_loss_weight), out=self.geo_out,
                                   deterministic=self.deterministic, scratch=self.geo_scratch)
                 constrain = self.geo_out["constrain"]
+            geo_on = constrain is not None
+            if self.w_uni != 0:   # constrain (+)= w U before the head reads it (no other term on: constrain = w U)
+                ops.uniform_loss(xe, contract=self.uni_contract, workspace=self.uni_ws, out=(t["uni_loss"], t["uni_grad"]))
+                constrain = self.geo_out["constrain"]
+                ops.uniform_fold(t["uni_loss"], None, None, self.w_uni, self.b, ne, constrain=constrain,
+                                 constrain_add=geo_on)
         late = self.late_join and self.geo_stream is not None
         if self.geo_stream is not None:     # join: the bookkeeping needs the constrain loss, the update the gradient
             self.ev_geo.record(self.geo_stream)
@@ -418,7 +429,11 @@ class AttackRunner:
             main.wait_event(self.ev_geo)
             check(lib.geoa3_attack_head_finish(st, t["ok"].data_ptr(), self._p(constrain), x.data_ptr(), step,
                                                search_step, s), "attack_head_finish")
-        g_geo = t["g_geo"] if constrain is not None else None
+        if self.w_uni != 0:   # d mean_b(c_b w U) / dx = w (sum_b c_b) / b dU/dx, unscaled like g_cls (geo stream joined)
+            ops.uniform_fold(t["uni_loss"], t["uni_grad"], t["scale_const"], self.w_uni, self.b, ne, g=t["g_cls"],
+                             g_add=g_cls is not None, stream=s)
+            g_cls = t["g_cls"]
+        g_geo = t["g_geo"] if geo_on else None
         if self.sub:   # torch.gather's backward (Lib/utility.py:185): scatter the sample's gradient to the full cloud
             for src, dst in ((g_cls, "g_cls_full"), (g_geo, "g_geo_full")):
                 if src is not None:
@@ -486,7 +501,8 @@ class AttackRunner:
         cfg, t = self.cfg, self.t
         vals = torch.stack([t["loss_n"].mean() * (self.b / float(self.global_batch)), t["cls_loss"].mean(),
                             self.geo_out["dis_loss"].mean(), self.geo_out["hd_loss"].mean(),
-                            self.geo_out["curv_loss"].mean()]).tolist()
+                            self.geo_out["curv_loss"].mean()] +
+                           ([self.t["uni_loss"]] if self.w_uni != 0 else [])).tolist()
         info = "[{5}/{6}][{0}/{1}][{2}/{3}] \t loss: {4:6.4f}\t".format(
             search_step + 1, cfg.binary_max_steps, step + 1, cfg.iter_max_steps, vals[0], i, loader_len)
         info += "cls_loss: {0:6.4f}\t".format(vals[1])
@@ -498,6 +514,8 @@ class AttackRunner:
             info += "hd_loss : {0:6.4f}\t".format(vals[3])
         if cfg.curv_loss_weight != 0:
             info += "curv_loss : {0:6.4f}\t".format(vals[4])
+        if self.w_uni != 0:
+            info += "uniform : {0:6.4f}\t".format(vals[5])
         return info
 
     def run(self, init_offsets: Optional[Sequence[Tensor]] = None, i: int = 0, loader_len: int = 1,

@@ -14,11 +14,12 @@ differentiates through it, a registered autograd formula.  `geoa3_amd.ops.knn_po
     geoa3::geo_loss_grad   CD / HD / L2 / curvature values and d constrain / d adv   Attacker/geoA3_attack.py:131-166
     geoa3::point_loss      chamfer / pseudo-chamfer / hausdorff / l2 with autograd    Lib/loss_utils.py:25-50
     geoa3::kappa_adv       _get_kappa_adv with autograd                               Lib/loss_utils.py:64-82
+    geoa3::uniform_loss    uniform_loss (one scalar for the batch) with autograd      Lib/loss_utils.py:151-189
     geoa3::pointnet_forward / _backward   PointNet.forward (eval) and its input gradient   Model/PointNet.py:132-160
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch.library import custom_op
@@ -209,6 +210,29 @@ def _kappa_adv_backward(ctx, gk, _gn, _gi, _gt):
 
 
 kappa_adv.register_autograd(_kappa_adv_backward, setup_context=_kappa_adv_setup)
+
+@custom_op("geoa3::uniform_loss", mutates_args=(), device_types="cuda")
+def uniform_loss(adv_pc: Tensor, percentages: List[float], radius: float, k: int, contract: int) -> Tuple[Tensor, Tensor]:
+    """uniform_loss on adv_pc [b,3,n] planar -> (U [] float32, dU / d adv [b,3,n]).  contract: -1 = the choice of
+    geoa3_amd.pointnet2.ext_contract_default, 0 / 1 = GEOA3_PN2_CONTRACT off / on."""
+    return ops.uniform_loss(_planar(adv_pc), percentages, radius, k, contract=None if contract < 0 else bool(contract))
+
+
+@uniform_loss.register_fake
+def _(adv_pc, percentages, radius, k, contract):
+    return adv_pc.new_empty((), dtype=_f32), adv_pc.new_empty(adv_pc.shape, dtype=_f32)
+
+
+def _uniform_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _uniform_backward(ctx, g, _gg):
+    (grad,) = ctx.saved_tensors
+    return grad * g, None, None, None, None
+
+
+uniform_loss.register_autograd(_uniform_backward, setup_context=_uniform_setup)
 
 # ------------------------------------------------------------------------------------------------ the victim
 import weakref

@@ -7,7 +7,7 @@ _forward_step composition (Attacker/geoA3_attack.py:131-166) and swap only the i
     Lib/loss_utils.py:25-26   norm_l2_loss          Lib/loss_utils.py:52-62   _get_kappa_ori
     Lib/loss_utils.py:28-35   chamfer_loss          Lib/loss_utils.py:64-82   _get_kappa_adv
     Lib/loss_utils.py:37-43   pseudo_chamfer_loss   Lib/loss_utils.py:84-97   curvature_loss
-    Lib/loss_utils.py:45-50   hausdorff_loss
+    Lib/loss_utils.py:45-50   hausdorff_loss        Lib/loss_utils.py:151-189 uniform_loss
 """
 from __future__ import annotations
 
@@ -55,3 +55,14 @@ def curvature_loss(adv_pc: Tensor, ori_pc: Tensor, adv_kappa: Tensor, ori_kappa:
     _, i_ao, _, _ = torch.ops.geoa3.nn1_pair(adv_pc, ori_pc, False)
     onenn_ori_kappa = torch.gather(ori_kappa, 1, i_ao.long())
     return ((adv_kappa - onenn_ori_kappa) ** 2).mean(-1)
+
+
+def uniform_loss(adv_pc: Tensor, percentages=[0.004, 0.006, 0.008, 0.010, 0.012], radius: float = 1.0, k: int = 2,
+                 contract=None) -> Tensor:
+    """The PU-GAN uniformity term: ONE float32 scalar for the whole batch (the mean runs over all rows of all instances),
+    differentiable w.r.t. adv_pc.  [b,3,n] when adv_pc.size(1) == 3, otherwise [b,n,3], as the reference decides.  What
+    the reference computes once Lib/loss_utils.py imports pointnet2_utils; contract: see
+    geoa3_amd.pointnet2.ext_contract_default (None = its choice)."""
+    x = adv_pc if adv_pc.size(1) == 3 else adv_pc.permute(0, 2, 1)
+    return torch.ops.geoa3.uniform_loss(x, [float(p) for p in percentages], float(radius), int(k),
+                                        -1 if contract is None else int(bool(contract)))[0]

@@ -151,6 +151,57 @@ def geo_loss_grad(adv: Tensor, ori: Tensor, *, normal_ori=None, kappa_ori=None, 
     return o
 
 
+UNIFORM_PERCENTAGES = (0.004, 0.006, 0.008, 0.010, 0.012)   # uniform_loss's defaults, Lib/loss_utils.py:151
+
+
+def uniform_workspace(B: int, N: int, device) -> Tensor:
+    """Workspace of geoa3_uniform_loss for [B,3,N] clouds."""
+    return torch.empty(int(_lib.load().geoa3_uniform_loss_workspace_bytes(B, N)), dtype=torch.uint8, device=device)
+
+
+def uniform_loss(pc: Tensor, percentages=UNIFORM_PERCENTAGES, radius: float = 1.0, k: int = 2,
+                 contract: Optional[bool] = None, workspace: Optional[Tensor] = None, out=None, want_idx: bool = False):
+    """The uniformity term of Lib/loss_utils.py:151-189 on pc [B,3,N] (planar) -> (U [] float32 -- one scalar for the
+    batch --, dU/dpc [B,3,N]); with want_idx also the sampler's indices [B,npoint] and the ball-query rows (a list of
+    [B,npoint,nsample_p], one per percentage).  contract: the sampler's and the ball queries' distances as
+    GEOA3_PN2_CONTRACT (None = the choice of geoa3_amd.pointnet2.ext_contract_default)."""
+    from .pointnet2 import _ext_flags
+    B, _, N = pc.shape
+    pcts = [float(p) for p in percentages]
+    if out is None:
+        out = (torch.empty((), device=pc.device, dtype=torch.float32),
+               torch.empty(B, 3, N, device=pc.device, dtype=torch.float32))
+    loss, grad = out
+    if workspace is None:
+        workspace = uniform_workspace(B, N, pc.device)
+    fps_idx = group_idx = None
+    npoint = int(N * 0.05)
+    ns = [int(N * (p * 4)) for p in pcts]
+    if want_idx:
+        fps_idx = torch.empty(B, max(npoint, 1), device=pc.device, dtype=torch.int32)
+        group_idx = torch.empty(B * max(npoint, 1) * max(sum(ns), 1), device=pc.device, dtype=torch.int32)
+    arr = (C.c_double * max(len(pcts), 1))(*pcts)
+    check(_lib.load().geoa3_uniform_loss(_p(pc, torch.float32), B, N, arr, len(pcts), float(radius), int(k),
+                                         _ext_flags(contract), _p(loss), _p(grad), _p(fps_idx), _p(group_idx),
+                                         _p(workspace), _stream()), "geoa3_uniform_loss")
+    if not want_idx:
+        return loss, grad
+    rows, o = [], 0
+    for n in ns:
+        rows.append(group_idx[o:o + B * npoint * n].view(B, npoint, n))
+        o += B * npoint * n
+    return loss, grad, fps_idx, rows
+
+
+def uniform_fold(loss: Tensor, grad: Optional[Tensor], scale_const: Optional[Tensor], w: float, B: int, N: int,
+                 constrain: Optional[Tensor] = None, constrain_add: bool = False, g: Optional[Tensor] = None,
+                 g_add: bool = False, stream: Optional[int] = None) -> None:
+    """geoa3_uniform_fold: constrain (+)= w U; g (+)= w (sum_b scale_const[b] / B) dU (geoA3_attack.py:171,176-178)."""
+    check(_lib.load().geoa3_uniform_fold(_p(loss), _p(grad), _p(scale_const), float(w), B, N, _p(constrain),
+                                         int(constrain_add), _p(g), int(g_add),
+                                         _stream() if stream is None else stream), "geoa3_uniform_fold")
+
+
 # ---------------------------------------------------------------------------------------------
 # Operator-level mirror of pytorch3d.ops (SURVEY 8b-1): [b,n,3] point-major arguments, int64 idx,
 # differentiable through `dists`.

@@ -518,6 +518,30 @@ int geoa3_sor_statistic(const float* pc, int B, int N, int K, float* dis, void* 
 int geoa3_sor_select(const float* dis, int B, int N, int mode, int drop_num, float alpha, int32_t* idx,
                      int32_t* count, float* stats, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Uniformity term (Lib/loss_utils.py:151-189, uniform_loss; Attacker/geoA3_attack.py:168-174, --uniform_loss_weight).
+ * ------------------------------------------------------------------------------------------ */
+/* loss [1] = U, ONE scalar for the batch: for every p of percentages[num_percentages] (p <- 4p, nsample = int(N p),
+ * r = sqrt(p radius), expect_len = float32(sqrt(float32(pi radius^2 p / nsample))), scale = (100 p)^2), the mean over all
+ * B * npoint * nsample rows of (u - expect_len)^2 / (expect_len + 1e-12), u = the mean of sqrt(|d| + 1e-12) over the k
+ * nearest other slots of the row's group (knn_points(g, g, k + 1), dists[:, :, 1:]), times scale; the sum over p divided
+ * by num_percentages.  Groups: ball_query(r, nsample) around the npoint = int(N * 0.05) centres of
+ * furthest_point_sample(pc, npoint) -- the bits of geoa3_pn2_furthest_point_sampling_ex / geoa3_pn2_ball_query_ex with
+ * the same `flags` (GEOA3_PN2_CONTRACT).  pc [B,3,N] planar; grad [B,3,N] = dU / d pc (required).  fps_idx [B,npoint] and
+ * group_idx (the ball-query rows of every p, one [B,npoint,nsample_p] block after the other) are optional outputs.
+ * Supported: 1 <= num_percentages <= 8, 1 <= k <= 8, every nsample in k+1 .. 512, N <= 8192 (GEOA3_ENOSUPPORT
+ * otherwise).  A non-finite coordinate makes U and its instance's gradient NaN.  Deterministic: repeated calls are bit
+ * identical.  workspace: geoa3_uniform_loss_workspace_bytes(B, N) bytes. */
+int64_t geoa3_uniform_loss_workspace_bytes(int B, int N);
+int geoa3_uniform_loss(const float* pc, int B, int N, const double* percentages, int num_percentages, double radius,
+                       int k, int flags, float* loss, float* grad, int32_t* fps_idx, int32_t* group_idx,
+                       void* workspace, void* stream);
+/* geoA3_attack.py:171,176-178 with constrain_loss += w * U: constrain [B] (optional) = (constrain_add ? constrain : 0)
+ * + w * loss[0]; g [B,3,N] (optional) = (g_add ? g : 0) + w * (sum_b scale_const[b] / B) * grad -- the gradient of
+ * mean_b(scale_const[b] * w * U), which couples the rows of the batch. */
+int geoa3_uniform_fold(const float* loss, const float* grad, const float* scale_const, float w, int B, int N,
+                       float* constrain, int constrain_add, float* g, int g_add, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
