@@ -31,16 +31,14 @@ class TnetWeights(C.Structure):
     """struct geoa3_tnet_weights"""
     _fields_ = [("K", C.c_int32)] + [(n, vp) for n in (
         "w1", "b1", "w2", "b2", "w3", "b3", "w3p", "w2t", "f1", "fb1", "f2", "fb2", "f3", "fb3",
-        "f1t", "f2t", "f3t", "w3h")] + [("w3h_unscale", C.c_float), ("w2h", vp), ("w2h_unscale", C.c_float), ("w3h16", vp),
-                                      ("w2th", vp), ("w2th_unscale", C.c_float)]
+        "f1t", "f2t", "f3t", "w3h")] + [("w3h_unscale", C.c_float), ("w2th", vp), ("w2th_unscale", C.c_float)]
 
 
 class PointNetWeights(C.Structure):
     """struct geoa3_pointnet_weights"""
     _fields_ = [("classes", C.c_int32), ("t3", TnetWeights), ("t64", TnetWeights)] + [(n, vp) for n in (
         "w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4", "w5", "b5", "w5p", "w4t", "w3t", "w2t",
-        "f1", "fb1", "f2", "fb2", "f3", "fb3", "f1t", "f2t", "f3t", "w5h")] + [("w5h_unscale", C.c_float), ("w4h", vp),
-                                                                                 ("w4h_unscale", C.c_float), ("w5h16", vp),
+        "f1", "fb1", "f2", "fb2", "f3", "fb3", "f1t", "f2t", "f3t", "w5h")] + [("w5h_unscale", C.c_float),
                                                                                  ("w4th", vp), ("w4th_unscale", C.c_float),
                                                                                  ("flags", C.c_int32)]
 
@@ -127,8 +125,8 @@ SIGNATURES = {
     "geoa3_smoothness": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_sor_statistic": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_sor_select": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp]),
-    "geoa3_debug_wide_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "geoa3_debug_wide_fwd": (C.c_int, [vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_debug_wide_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "geoa3_debug_wide_fwd": (C.c_int, [vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_pn2_group_points_grad_sums": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_pn2_group_shift_relu": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_pn2_shift_relu": (C.c_int, [vp, vp, C.c_long, C.c_int, vp]),
@@ -151,7 +149,7 @@ _lib = None
 
 ENOSUPPORT = -3   # GEOA3_ENOSUPPORT
 PN2_CONTRACT = 1   # GEOA3_PN2_CONTRACT
-ABI_VERSION = 600  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
+ABI_VERSION = 601  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
 
 
 class Geoa3Error(RuntimeError):

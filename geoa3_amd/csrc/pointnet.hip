@@ -171,25 +171,10 @@ int fc(const float* X, int K, const float* W, const float* bias, float* Y, int N
   return launch_fc(a, s);
 }
 
-// fused: the 64 -> 128 layer in front (weights w2 / fragments w2h / bias b2) is evaluated in the wide kernel's staging pass
-// from h64 [B][64][N] (or, with x3, from relu(w1 x3 + b1)); its relu gate goes to m128, its activation nowhere
-struct FrontLayer {
-  const void* w2h; float w2_unscale; const float* w2; const float* b2;
-  const float* h64; const float* x3; const float* w1; const float* b1;
-  unsigned long long* m128;
-};
 int wide(const float* X, const float* W, const void* Wh, float unscale, const float* bias, float* out, int* arg,
-         unsigned long long* keys, int taps, int B, int N, hipStream_t s, const FrontLayer* f = nullptr,
-         const void* Wh16 = nullptr, int* hits = nullptr, int* hoff = nullptr) {
+         unsigned long long* keys, int taps, int B, int N, hipStream_t s, int* hits, int* hoff) {
   WideArgs a{};
-  a.Wh16 = Wh16;
   if (pre_lists(N)) { a.hits = hits; a.hoff = hoff; }
-  if (f) {
-    a.W2h = f->w2h; a.w2_unscale = f->w2_unscale; a.W2f = f->w2; a.b2 = f->b2;
-    a.Xin = f->h64; a.sXinb = (long)64 * N; a.ldXin = N;
-    a.x3 = f->x3; a.w1 = f->w1; a.b1 = f->b1;
-    a.Ymask = f->m128;
-  }
   a.keys = keys;
   a.keys_clean = 1;   // zeroed once per forward; every finalize leaves them zero
   a.Wh = Wh; a.unscale = unscale;
@@ -231,12 +216,7 @@ int tnet_tail_fwd(const geoa3_tnet_weights& t, const float* act64, const float* 
                   unsigned long long* m128, float* pooled,
                   int* arg, float* f4, float* f5, float* T, unsigned long long* keys, int B, int N, hipStream_t s,
                   int* hits, int* hoff, bool have128 = false) {
-  if (have128) {   // act128 (and m128) already produced by the trunk's chain kernel
-    TRY(wide(act128, t.w3p, t.w3h, t.w3h_unscale, t.b3, pooled, arg, keys, 1, B, N, s, nullptr, t.w3h16, hits, hoff));
-  } else if (tl_split && t.w2h) {   // conv2 (behind conv1 for the 3-channel T-Net) inside the wide kernel: act128 is never written
-    FrontLayer f{t.w2h, t.w2h_unscale, t.w2, t.b2, act64, act64 ? nullptr : x3, t.w1, t.b1, m128};
-    TRY(wide(nullptr, t.w3p, t.w3h, t.w3h_unscale, t.b3, pooled, arg, keys, 1, B, N, s, &f, nullptr, hits, hoff));
-  } else {
+  if (!have128) {   // (have128: act128 and m128 already produced by the trunk's chain kernel)
     if (act64) TRY(conv(act64, 64, t.w2, t.b2, act128, 128, B, N, true, nullptr, false, s, m128));
     else if (tl_split && fuse_chain()) {   // conv1 + conv2 of the 3-channel T-Net: the chain kernel with one stage
       ConvChainArgs a{};
@@ -245,8 +225,8 @@ int tnet_tail_fwd(const geoa3_tnet_weights& t, const float* act64, const float* 
       a.st[0] = ChainStage{t.w2, 0, t.b2, act128, (long)128 * N, m128, 128};
       TRY(launch_conv_chain(a, s));
     } else TRY(conv_first(x3, nullptr, t.w1, t.b1, t.w2, t.b2, act128, 128, B, N, s, m128));
-    TRY(wide(act128, t.w3p, t.w3h, t.w3h_unscale, t.b3, pooled, arg, keys, 1, B, N, s, nullptr, t.w3h16, hits, hoff));
   }
+  TRY(wide(act128, t.w3p, t.w3h, t.w3h_unscale, t.b3, pooled, arg, keys, 1, B, N, s, hits, hoff));
   TRY(fc(pooled, 1024, t.f1, t.fb1, f4, 512, B, true, nullptr, s));
   TRY(fc(f4, 512, t.f2, t.fb2, f5, 256, B, true, nullptr, s));
   TRY(fc(f5, 256, t.f3, t.fb3, T, t.K * t.K, B, false, nullptr, s));
@@ -329,7 +309,7 @@ extern "C" int geoa3_pointnet_forward(const geoa3_pointnet_weights* pw, const fl
   // input transform (Model/PointNet.py:137-138)
   TRY(tnet_tail_fwd(p.t3, nullptr, x, w.a2, w.m_a2, w.p3, w.i3, w.tf4, w.tf5, w.T3, w.keys, B, N, s, w.hl3, w.ho3));
   const bool chain = tl_split && fuse_chain();
-  if (chain && !p.t64.w2h) {
+  if (chain) {
     // trunk conv1, conv2 (:139-140) and the feature transform's conv1, conv2 (:78-80) in one kernel: h2 is written (the
     // backward and conv3 read it), c1 exists only as gate bits, c2 is the T-Net's 1024-wide layer's input
     ConvChainArgs a{};
@@ -357,8 +337,7 @@ extern "C" int geoa3_pointnet_forward(const geoa3_pointnet_weights* pw, const fl
     g.M = 64; g.Nout = 64; g.K = 64; g.batch = B;
     TRY(launch_fc(g, s));
   }
-  const bool chain34 = chain && !p.w4h;
-  if (chain34) {   // conv3, conv4 in one kernel: h3 exists only as gate bits
+  if (chain) {   // conv3, conv4 in one kernel: h3 exists only as gate bits
     ConvChainArgs a{};
     a.X = w.h2; a.sXb = (long)64 * N; a.ldX = N;
     a.N = N; a.B = B; a.ns = 2;
@@ -375,17 +354,11 @@ extern "C" int geoa3_pointnet_forward(const geoa3_pointnet_weights* pw, const fl
     a.Ymask = w.m_h3;
     a.Co = 64; a.K = 64; a.N = N; a.B = B; a.relu = 1;
     TRY(launch_conv_cm(a, s));
-  }
-  // conv4, conv5 + max (:145-147)
-  if (chain34) {
-    TRY(wide(w.h4, p.w5p, p.w5h, p.w5h_unscale, p.b5, w.p5, w.i5, w.keys, 3, B, N, s, nullptr, p.w5h16, w.hl5, w.ho5));
-  } else if (tl_split && p.w4h) {   // conv4 inside conv5's staging pass: h4 is never written
-    FrontLayer f{p.w4h, p.w4h_unscale, p.w4, p.b4, w.h3, nullptr, nullptr, nullptr, w.m_h4};
-    TRY(wide(nullptr, p.w5p, p.w5h, p.w5h_unscale, p.b5, w.p5, w.i5, w.keys, 3, B, N, s, &f, nullptr, w.hl5, w.ho5));
-  } else {
+    // conv4 (:145)
     TRY(conv(w.h3, 64, p.w4, p.b4, w.h4, 128, B, N, true, nullptr, false, s, w.m_h4));
-    TRY(wide(w.h4, p.w5p, p.w5h, p.w5h_unscale, p.b5, w.p5, w.i5, w.keys, 3, B, N, s, nullptr, p.w5h16, w.hl5, w.ho5));
   }
+  // conv5 + max (:146-147)
+  TRY(wide(w.h4, p.w5p, p.w5h, p.w5h_unscale, p.b5, w.p5, w.i5, w.keys, 3, B, N, s, w.hl5, w.ho5));
   // classifier head (:150-152), dropout is the identity in eval mode
   TRY(fc(w.p5, 1024, p.f1, p.fb1, w.f6, 512, B, true, nullptr, s));
   TRY(fc(w.f6, 512, p.f2, p.fb2, w.f7, 256, B, true, nullptr, s));

@@ -116,29 +116,19 @@ struct WideArgs {
   float* out; int* arg;                       // [B][Co]
   unsigned long long* keys;                   // [B][Co] scratch of the column-major kernel (packed running maxima)
   int Co, N, B, taps;
-  const void* Wh;                             // split-fp16 fragments (pointnet_wide_split.hip) or null = fp32 MFMA
-  const void* Wh16;                           // the same weights as 16x16x32 fragments (pointnet_wide16.hip); takes precedence
+  const void* Wh;                             // split-fp16 fragments or null = fp32 MFMA: taps 1 in the 32x32x16 layout of
+                                              // pointnet_wide_split.hip, taps 3 in the 16x16x32 layout of pointnet_wide16.hip
   float unscale;                              // 1 / (power-of-two scale of Wh)
   int keys_clean;                             // 1: keys are already zero (wide_finalize_kernel leaves them zero): no memset
-  int variant;                                // tuning variant of the split kernel (geoa3_debug_wide_fwd; 0 = shipped)
-  // split kernel only: the layer in front of the wide one folded into its staging pass -- X[b][c][n] =
-  // relu(W2 h + b2)[c][n] is computed per tile (X unused, never written) from the 64-channel activation h = Xin, or,
-  // with x3, from h = relu(w1 x3 + b1); Ymask receives the relu gate of X as bits ([B][ceil(N/64)][128] 64-bit words)
-  const void* W2h; float w2_unscale;          // pack_wide_split fragments of W2 [128][64] and 1 / their scale
-  const float* W2f;                           // the same weights [128][64] fp32 (conv5's two halo points per tile)
-  const float* b2;                            // [128]
-  const float* Xin; long sXinb; int ldXin;    // [B][64][N]
-  const float* x3; const float* w1; const float* b1;   // [B][3][N], [64][3], [64]
-  unsigned long long* Ymask;
   unsigned long long* stamps;                 // diagnostics (tools/bench_wide.py --stamps): s_memtime trace of workgroup 0
   // with both (Co = 1024, N <= 4096): the finalize pass also builds the sparse backward's hit lists -- hits [B][Co taps]
   // = (co * taps + tap) | (column << 16) sorted by (column, chunk of 64 channels, tap, channel), hoff [B][N + 1] the
   // columns' start offsets (WideBwdArgs::hits / hoff)
   int* hits; int* hoff;
 };
-int launch_wide_max(const WideArgs& a, hipStream_t s);          // dispatches on a.Wh
-int launch_wide_max_split(const WideArgs& a, hipStream_t s);    // pointnet_wide_split.hip
-int launch_wide_max_split16(const WideArgs& a, hipStream_t s);  // pointnet_wide16.hip
+int launch_wide_max(const WideArgs& a, hipStream_t s);          // dispatches on a.Wh and a.taps
+int launch_wide_max_split(const WideArgs& a, hipStream_t s);    // pointnet_wide_split.hip (taps 1)
+int launch_wide_max_split16(const WideArgs& a, hipStream_t s);  // pointnet_wide16.hip (taps 3)
 void launch_wide_finalize(const WideArgs& a, hipStream_t s);    // keys -> out (bias + relu), arg
 
 // packed running maximum of the 1024-wide layers: (order-preserving value bits, ~point index) under a 64-bit atomicMax
@@ -170,8 +160,6 @@ struct WideBwdArgs {
   const float* x3; const float* w1; const float* b1; float* dx3;
   const int* hits; const int* hoff;           // launch_wide_bwd_conv: the lists built by the forward's finalize pass (or null:
                                               // every workgroup builds its tile's lists from g / arg)
-  int form;                                   // 0 = register accumulation over per-column lists (default), 1 = the first
-                                              // form (LDS accumulation); same sums in the same order
 };
 int launch_wide_max_bwd(const WideBwdArgs& a, hipStream_t s);
 int launch_wide_bwd_conv(const WideBwdArgs& a, hipStream_t s);

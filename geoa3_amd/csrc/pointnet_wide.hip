@@ -4,7 +4,7 @@
 // 64-point tiles are combined through an atomic max on packed (value, point) keys.  relu and the folded BN
 // bias commute with the max, so they are applied once to the 1024 maxima.
 // The backward is sparse -- only the arg-max column of every channel carries gradient -- and is a
-// deterministic gather-by-owner accumulation in LDS (no atomics).
+// deterministic gather-by-owner accumulation (no atomics).
 #include "pointnet_kernels.h"
 #include "profile.h"
 
@@ -274,134 +274,14 @@ __global__ __launch_bounds__(1024) void wide_finalize_hits_kernel(unsigned long 
 }
 
 // ------------------------------------------------------------------------------------------
-// Sparse backward.  One workgroup per (instance, WB_COLS-point tile), split in NP parts of WB_COLS/NP columns with 128
-// threads each; thread (ci, part) owns row ci of its part, so no two threads ever touch the same accumulator
-// and the summation order is fixed (deterministic, no atomics).
-// Per block of WB_BLOCK output channels: the first wave of each part compacts the (channel, tap) pairs whose
-// arg-max column falls into its part into an LDS hit list (ballot + popcount, in (co, tap) order, the upstream
-// gradient stored next to it); then the 128 threads of the part walk ONLY the hits, WB_BATCH independent
-// weight-row loads in flight.  The walk is L2-latency bound and the write-out bandwidth bound; they do not overlap
-// inside a workgroup, so the tile is kept small (64 columns, 33 KB of accumulators): three workgroups per CU.
-// ------------------------------------------------------------------------------------------
-constexpr int WB_BATCH = 16;
-
-template <int TAPS, int NP, int WB_BLOCK, int WB_COLS>   // WB_BLOCK: output channels per compaction round
-__global__ __launch_bounds__(128 * NP) void wide_max_bwd_kernel(WideBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int PC = WB_COLS / NP;                                            // columns per part
-  float* s_acc = smem;                                                        // [128 ci][WB_COLS + 1]
-  int* s_hit = reinterpret_cast<int*>(smem + WM_CI * (WB_COLS + 1));          // [NP][WB_BLOCK*TAPS]
-  float* s_g = reinterpret_cast<float*>(s_hit + NP * WB_BLOCK * TAPS);        // [NP][WB_BLOCK*TAPS]
-  int* s_cnt = reinterpret_cast<int*>(s_g + NP * WB_BLOCK * TAPS);            // [NP]
-  const int tid = threadIdx.x, b = blockIdx.y, m0 = blockIdx.x * WB_COLS;
-  const int ci = tid & 127, part = tid >> 7, lane = tid & 63;
-  const bool builder = (tid & 127) < 64;                                      // first wave of each part
-  const float* gb = a.g + (size_t)b * a.Co;
-  const int* argb = a.arg + (size_t)b * a.Co;
-  int* hits = s_hit + part * WB_BLOCK * TAPS;
-  float* hitg = s_g + part * WB_BLOCK * TAPS;
-  float* row = s_acc + ci * (WB_COLS + 1);
-  for (int j = part * PC; j < part * PC + PC; ++j) row[j] = 0.f;
-  const int lo = m0 + part * PC, hi = lo + PC;
-
-  for (int cb = 0; cb < a.Co; cb += WB_BLOCK) {
-    __syncthreads();  // the previous round's list has been consumed
-    if (builder) {
-      int cnt = 0;
-      for (int c0 = cb; c0 < min(cb + WB_BLOCK, a.Co); c0 += 64) {
-        const int co = c0 + lane;
-        const bool in = co < a.Co;
-        const float g = in ? gb[co] : 0.f;
-        const int base = (in ? argb[co] : 0) - TAPS / 2;
-#pragma unroll
-        for (int tap = 0; tap < TAPS; ++tap) {
-          const int m = base + tap;
-          const bool hit = g != 0.f && m >= lo && m < hi;
-          const unsigned long long mask = __ballot(hit);
-          if (hit) {
-            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-            hits[slot] = (co * TAPS + tap) | ((m - m0) << 16);
-            hitg[slot] = g;
-          }
-          cnt += __popcll(mask);
-        }
-      }
-      if (lane == 0) s_cnt[part] = cnt;
-    }
-    __syncthreads();
-    const int cnt = s_cnt[part];
-    for (int h0 = 0; h0 < cnt; h0 += WB_BATCH) {
-      float w[WB_BATCH], gg[WB_BATCH];
-      int mm[WB_BATCH];
-#pragma unroll
-      for (int u = 0; u < WB_BATCH; ++u) {
-        const bool ok = h0 + u < cnt;
-        const int e = hits[ok ? h0 + u : cnt - 1];
-        w[u] = a.W[(size_t)(e & 0xffff) * WM_CI + ci];   // row co*TAPS + tap of the [Co*TAPS][128] weight view
-        gg[u] = ok ? hitg[h0 + u] : 0.f;
-        mm[u] = e >> 16;
-      }
-#pragma unroll
-      for (int u = 0; u < WB_BATCH; ++u) row[mm[u]] += w[u] * gg[u];
-    }
-  }
-  __syncthreads();
-  // write out with the relu gate of the layer input: 4 consecutive points per thread (16-byte loads / stores)
-  float* dX = a.dX + (size_t)b * a.sXb;
-  if (a.Zmask && WB_COLS == 64) {   // the gate as one bit per element: one 64-bit word per (channel, this tile)
-    const unsigned long long* mk = a.Zmask + ((size_t)b * ((a.N + 63) >> 6) + blockIdx.x) * WM_CI;   // [B][tile][ci]
-    const bool vec = (a.ldX & 3) == 0;
-#pragma unroll 4
-    for (int e = tid; e < WM_CI * (WB_COLS / 4); e += 128 * NP) {
-      const int c = e / (WB_COLS / 4), j = (e - c * (WB_COLS / 4)) * 4;
-      const int m = m0 + j;
-      const float* sa = s_acc + c * (WB_COLS + 1) + j;
-      const unsigned bits = (unsigned)(mk[c] >> j) & 15u;
-      if (vec && m + 3 < a.N) {
-        float4 v;
-        v.x = bits & 1u ? sa[0] : 0.f;
-        v.y = bits & 2u ? sa[1] : 0.f;
-        v.z = bits & 4u ? sa[2] : 0.f;
-        v.w = bits & 8u ? sa[3] : 0.f;
-        *reinterpret_cast<float4*>(dX + (size_t)c * a.ldX + m) = v;
-      } else {
-        for (int i = 0; i < 4; ++i)
-          if (m + i < a.N) dX[(size_t)c * a.ldX + m + i] = (bits >> i) & 1u ? sa[i] : 0.f;
-      }
-    }
-    return;
-  }
-  const float* Z = a.Z + (size_t)b * a.sZb;
-  const bool vec = ((a.ldX | a.ldZ) & 3) == 0;
-#pragma unroll 4
-  for (int e = tid; e < WM_CI * (WB_COLS / 4); e += 128 * NP) {
-    const int c = e / (WB_COLS / 4), j = (e - c * (WB_COLS / 4)) * 4;
-    const int m = m0 + j;
-    const float* sa = s_acc + c * (WB_COLS + 1) + j;
-    if (vec && m + 3 < a.N) {
-      const float4 z = *reinterpret_cast<const float4*>(Z + (size_t)c * a.ldZ + m);
-      float4 v;
-      v.x = z.x > 0.f ? sa[0] : 0.f;
-      v.y = z.y > 0.f ? sa[1] : 0.f;
-      v.z = z.z > 0.f ? sa[2] : 0.f;
-      v.w = z.w > 0.f ? sa[3] : 0.f;
-      *reinterpret_cast<float4*>(dX + (size_t)c * a.ldX + m) = v;
-    } else {
-      for (int i = 0; i < 4; ++i)
-        if (m + i < a.N) dX[(size_t)c * a.ldX + m + i] = Z[(size_t)c * a.ldZ + m + i] > 0.f ? sa[i] : 0.f;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// Sparse backward, second form (the default): the same sums in the same order, accumulated in REGISTERS.
+// Sparse backward, accumulated in REGISTERS (deterministic, no atomics).
 // One workgroup per (instance, 64-point tile), 8 wavefronts.  (1) the (channel, tap) pairs whose arg-max lands in the
 // tile are compacted into a flat list in a fixed order (ballot + popcount); (2) a stable placement groups them by
 // column (wave w owns 8 columns and passes over the flat list in order: no sort, no order left to chance); (3) the
 // grouped list is cut into equal shares, one per wave: eight weight rows (512 B each, lane = two input channels) are in
 // flight per step, the running column's sum lives in two registers and is stored to the LDS tile when the column
-// changes -- no read-modify-write chain through LDS, which is what bounded the first form (97 / 151 us for 64 / 192
-// hits per tile); (4) the tile is written out with the relu gate of the layer input as before.
+// changes -- no read-modify-write chain through LDS, which is what bounded an earlier form that accumulated in LDS (97 /
+// 151 us for 64 / 192 hits per tile); (4) the tile is written out with the relu gate of the layer input.
 // ------------------------------------------------------------------------------------------
 constexpr int BW2_WAVES = 8, BW2_THREADS = 64 * BW2_WAVES;
 template <int TAPS>
@@ -649,8 +529,7 @@ void launch_wide_finalize(const WideArgs& a, hipStream_t s) {
 }
 
 int launch_wide_max(const WideArgs& a, hipStream_t s) {
-  if (a.Wh16 && !a.W2h) return launch_wide_max_split16(a, s);
-  if (a.Wh) return launch_wide_max_split(a, s);
+  if (a.Wh) return a.taps == 3 ? launch_wide_max_split16(a, s) : launch_wide_max_split(a, s);
   if (a.Co != 8 * WM_CO || (a.taps != 1 && a.taps != 3) || !a.keys) return GEOA3_ENOSUPPORT;
   const int tag = a.taps == 3 ? GEOA3_PROF_CONV5 : GEOA3_PROF_TNETWIDE;
   geoa3_prof_begin(tag, s);
@@ -668,45 +547,28 @@ int launch_wide_max(const WideArgs& a, hipStream_t s) {
   return GEOA3_OK;
 }
 
-template <int TAPS, int NP, int WB_BLOCK, int WB_COLS>
-static void launch_wide_bwd_variant(const WideBwdArgs& a, hipStream_t s) {
-  dim3 grid((a.N + WB_COLS - 1) / WB_COLS, a.B);
-  const size_t lds = ((size_t)WM_CI * (WB_COLS + 1) + 2 * (size_t)NP * WB_BLOCK * TAPS + NP) * sizeof(float);
-  auto kern = wide_max_bwd_kernel<TAPS, NP, WB_BLOCK, WB_COLS>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, grid, dim3(128 * NP), lds, s, a);
-}
-
 int launch_wide_max_bwd(const WideBwdArgs& a, hipStream_t s) {
   if (a.taps != 1 && a.taps != 3) return GEOA3_ENOSUPPORT;
-  // tile width / parts / compaction block picked on hardware (tools/bench_widebwd.py): 64-column tiles leave room for
-  // three workgroups per CU, so one workgroup's write-out overlaps its neighbours' hit walks (95 / 150 us)
-  if (a.form == 1) {   // the first form (LDS accumulation), kept for tools/bench_widebwd.py and the cross-check test
-    if (a.taps == 1) launch_wide_bwd_variant<1, 2, 256, 64>(a, s);
-    else launch_wide_bwd_variant<3, 2, 128, 64>(a, s);
+  if (a.Co * a.taps > 0xffff) return GEOA3_ENOSUPPORT;
+  dim3 grid((a.N + 63) / 64, a.B);
+  const size_t region = (size_t)WM_CI * 65 > 2 * (size_t)a.Co * a.taps ? (size_t)WM_CI * 65 : 2 * (size_t)a.Co * a.taps;
+  const size_t lds = (region + (size_t)a.Co * a.taps + 65 + 2 * BW2_WAVES + 1 + BW2_WAVES * WM_CI + 3) * sizeof(float);
+  if (a.taps == 1) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wide_max_bwd2_kernel<1>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(wide_max_bwd2_kernel<1>, grid, dim3(BW2_THREADS), lds, s, a);
   } else {
-    if (a.Co * a.taps > 0xffff) return GEOA3_ENOSUPPORT;
-    dim3 grid((a.N + 63) / 64, a.B);
-    const size_t region = (size_t)WM_CI * 65 > 2 * (size_t)a.Co * a.taps ? (size_t)WM_CI * 65 : 2 * (size_t)a.Co * a.taps;
-    const size_t lds = (region + (size_t)a.Co * a.taps + 65 + 2 * BW2_WAVES + 1 + BW2_WAVES * WM_CI + 3) * sizeof(float);
-    if (a.taps == 1) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wide_max_bwd2_kernel<1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(wide_max_bwd2_kernel<1>, grid, dim3(BW2_THREADS), lds, s, a);
-    } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wide_max_bwd2_kernel<3>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(wide_max_bwd2_kernel<3>, grid, dim3(BW2_THREADS), lds, s, a);
-    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wide_max_bwd2_kernel<3>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(wide_max_bwd2_kernel<3>, grid, dim3(BW2_THREADS), lds, s, a);
   }
   GEOA3_CHECK_LAUNCH();
   return GEOA3_OK;
 }
 
 extern "C" int geoa3_debug_wide_bwd(const float* g, const int32_t* arg, const float* W, const float* Z, float* dX, int B,
-                                    int N, int taps, int form, void* stream) {
+                                    int N, int taps, void* stream) {
   WideBwdArgs a{};
-  a.form = form;
   a.g = g; a.arg = arg; a.W = W;
   a.Z = Z; a.sZb = (long)128 * N; a.ldZ = N;
   a.dX = dX; a.sXb = (long)128 * N; a.ldX = N;

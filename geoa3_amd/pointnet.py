@@ -43,8 +43,8 @@ def pack_wide_fragments(w: Tensor, taps: int) -> Tensor:
     return v.permute(0, 2, 3, 4, 1, 5).reshape(-1, 4).contiguous()   # T, tap, j, (h, r) = lane, i
 
 
-def pack_wide_split(w: Tensor, taps: int):
-    """[Co, taps*128] fp32 -> (fragments, unscale) for csrc/pointnet_wide_split.hip: v = w * 2^e (max |v| in
+def pack_wide_split(w: Tensor):
+    """[Co, K] fp32 -> (fragments, unscale) for csrc/pointnet_wide_split.hip: v = w * 2^e (max |v| in
     [2^13, 2^14)), hi = rn16(v), lo = rn16(v - hi) -- |v - hi - lo| <= 2^-24 |v| while lo is a normal fp16, i.e. for
     every weight above 2^-16 of the largest -- as an fp16 tensor
     [T = Co/32][s = K/16][piece][lane = 32h + r][j]  =  piece(w[32T + r][16s + 8h + j]);  unscale = 2^-e."""
@@ -75,13 +75,8 @@ def pack_wide_split16(w: Tensor):
 
 
 def wide_shape(layer: str = "conv5") -> int:
-    """MFMA shape of a split 1024-wide layer: 16 = v_mfma_f32_16x16x32_f16 (pointnet_wide16.hip), 32 =
-    v_mfma_f32_32x32x16_f16 (pointnet_wide_split.hip).  Measured on MI355X: conv5 (K = 384 per group) 0.495 -> 0.444 ms on
-    the 16x16x32 shape, the T-Nets' conv3 (K = 128 per group: a third of the MFMAs between two epilogues) 0.182 -> 0.292 ms
-    -- so conv5 takes 16, the T-Nets 32.  (GEOA3_WIDE_SHAPE_TNET / GEOA3_WIDE_SHAPE_CONV5 = 16 | 32: A/B runs of tools/.)"""
-    env = os.environ.get("GEOA3_WIDE_SHAPE_CONV5" if layer == "conv5" else "GEOA3_WIDE_SHAPE_TNET")
-    if env in ("16", "32"):
-        return int(env)
+    """MFMA shape of a split 1024-wide layer, for naming its kernel (bench.py): conv5 runs on 16x16x32
+    (pointnet_wide16.hip), the T-Nets' conv3 on 32x32x16 (pointnet_wide_split.hip)."""
     return 16 if layer == "conv5" else 32
 
 
@@ -101,10 +96,8 @@ def pack_tnet(sd: Dict[str, Tensor], prefix: str, K: int) -> Dict[str, Tensor]:
     for n in ("f1", "f2", "f3"):
         out[n + "t"] = out[n].t()
     out = {k: v.float().contiguous() for k, v in out.items()}
-    out["w3h"], out["w3h_unscale"] = pack_wide_split(out["w3"], 1)
-    out["w2h"], out["w2h_unscale"] = pack_wide_split(out["w2"], 1)
-    out["w3h16"], _ = pack_wide_split16(out["w3"])
-    out["w2th"], out["w2th_unscale"] = pack_wide_split(out["w2t"], 1)
+    out["w3h"], out["w3h_unscale"] = pack_wide_split(out["w3"])
+    out["w2th"], out["w2th_unscale"] = pack_wide_split(out["w2t"])
     return out
 
 
@@ -127,10 +120,8 @@ def pack_pointnet(sd: Dict[str, Tensor]) -> Dict[str, object]:
     for n in ("f1", "f2", "f3"):
         t[n + "t"] = t[n].t()
     out.update({k: v.float().contiguous() for k, v in t.items()})
-    out["w5h"], out["w5h_unscale"] = pack_wide_split(out["w5"], 3)
-    out["w4h"], out["w4h_unscale"] = pack_wide_split(out["w4"], 1)
-    out["w5h16"], _ = pack_wide_split16(out["w5"])
-    out["w4th"], out["w4th_unscale"] = pack_wide_split(out["w4t"], 1)
+    out["w5h"], out["w5h_unscale"] = pack_wide_split16(out["w5"])
+    out["w4th"], out["w4th_unscale"] = pack_wide_split(out["w4t"])
     return out
 
 
@@ -147,13 +138,6 @@ def default_wide_mode() -> str:
     if mode not in WIDE_MODES:
         raise ValueError("GEOA3_WIDE_MODE must be one of %s" % (WIDE_MODES,))
     return mode
-
-
-def fuse_front() -> bool:
-    """The 64 -> 128 layers in front of the three 1024-wide layers evaluated inside the wide kernels' staging pass (the
-    library supports it: geoa3_tnet_weights.w2h / geoa3_pointnet_weights.w4h).  Same results to rounding, but measured
-    SLOWER on MI355X (conv5 0.50 -> 0.71 ms against 52-60 us per convolution saved): never handed over by this host."""
-    return False
 
 
 # A/B switches of the library (geoa3_pointnet_weights.flags; the library itself reads no environment): bit 0 / bit 1 select
@@ -184,14 +168,8 @@ class PackedPointNet:
             return d.data_ptr()
 
         def pick(p: Dict[str, object], name: str):
-            if name in ("w3h", "w5h", "w2h", "w4h") and (not split or (name in ("w2h", "w4h") and not fuse_front())):
-                return None
-            if name in ("w2th", "w4th") and not split:
-                return None
-            if name == "w5h16" and (not split or wide_shape("conv5") != 16):
-                return None
-            if name == "w3h16" and (not split or wide_shape("tnet") != 16):
-                return None
+            if name in ("w3h", "w5h", "w2th", "w4th") and not split:
+                return None                    # split fragments only in f16x2 mode
             return dev(p[name])
 
         def tnet(p: Dict[str, Tensor], K: int) -> TnetWeights:
@@ -306,7 +284,7 @@ class PointNet(nn.Module):
         self._handle = library.register_net(self)
 
     def _weights_key(self, device):
-        return (str(device), self.wide_mode or default_wide_mode(), fuse_front(), wide_shape("conv5"), wide_shape("tnet")) + tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+        return (str(device), self.wide_mode or default_wide_mode()) + tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
     def packed(self, device) -> PackedPointNet:
         key = self._weights_key(device)

@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 600
+#define GEOA3_ABI_VERSION 601
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -169,17 +169,11 @@ typedef struct geoa3_tnet_weights {   /* transform_net, Model/PointNet.py:56-94 
   const float *f2, *fb2;    /* fc2+bn5 [256,512]  */
   const float *f3, *fb3;    /* fc3     [K*K,256]  */
   const float *f1t, *f2t, *f3t; /* transposes: [1024,512], [512,256], [256,K*K] */
-  const void *w3h;          /* optional (NULL = fp32 MFMA): w3 as split-fp16 fragments, see w5h */
-  float w3h_unscale;
-  const void *w2h;          /* optional, with w3h: w2 as split-fp16 fragments (same packing, K = 64).  Given, conv2 (and
-                               conv1 of the 3-channel T-Net) is evaluated inside conv3's staging pass: its [B,128,N]
-                               activation is never written, only its relu gate bits */
-  float w2h_unscale;
-  const void *w3h16;        /* optional, with w3h: the same split weights in 16x16x32 fragment order
-                               [T = co/16][s = k/32][piece][lane][j] = piece(w3[16T + (lane&15)][32s + 8(lane>>4) + j])
-                               (same scale: w3h_unscale): the layer then runs on `v_mfma_f32_16x16x32_f16`
-                               (csrc/pointnet_wide16.hip) -- same arithmetic, higher sustained clock */
-  const void *w2th;         /* optional, with w3h: w2t [64,128] as split-fp16 fragments (the packing of w5h, T = row/32, K = 128):
+  const void *w3h;          /* optional (NULL = fp32 MFMA; see w5h): v = w3 * 2^e as split-fp16 pieces in MFMA 32x32x16
+                               fragment order [T = co/32][s = k/16][piece hi,lo][lane 0..63][j 0..7] = piece(w3[32T +
+                               (lane&31)][16s + 8(lane>>5) + j]) (csrc/pointnet_wide_split.hip) */
+  float w3h_unscale;        /* 2^-e */
+  const void *w2th;         /* optional, with w3h: w2t [64,128] as split-fp16 fragments (the packing of w3h, T = row/32, K = 128):
                                the A operands of the backward's fused kernel (sparse gradient of conv3 + conv2's backward in
                                one launch).  NULL: the two run as separate kernels (same bits, slower) */
   float w2th_unscale;
@@ -208,17 +202,14 @@ typedef struct geoa3_pointnet_weights {  /* PointNet, Model/PointNet.py:96-160 *
   const float *f3, *fb3;    /* fc3     [classes,256] */
   const float *f1t, *f2t, *f3t; /* [1024,512] [512,256] [256,classes] */
   const void *w5h;          /* optional (NULL = the 1024-wide layers run on the fp32 MFMA): v = w5 * 2^e as TWO fp16 values
-                               per weight, hi = rn16(v), lo = rn16(v - hi), in MFMA 32x32x16 fragment order
-                               [T = co/32][s = k/16][piece hi,lo][lane 0..63][j 0..7] = piece(w5[32T + (lane&31)][16s +
-                               8(lane>>5) + j]); the layer then evaluates a*w = a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on the
-                               f16 matrix pipe with fp32 accumulation (csrc/pointnet_wide_split.hip).  Both or neither
+                               per weight, hi = rn16(v), lo = rn16(v - hi), in MFMA 16x16x32 fragment order
+                               [T = co/16][s = k/32][piece hi,lo][lane 0..63][j 0..7] = piece(w5[16T + (lane&15)][32s +
+                               8(lane>>4) + j]); the layer then evaluates a*w = a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on the
+                               f16 matrix pipe with fp32 accumulation (csrc/pointnet_wide16.hip).  Both or neither
                                of the T-Nets' w3h must be given with it.  Given, the 64/128-wide convolutions and the
                                Gram product of the backward use the same arithmetic (they split their fp32 weights
                                themselves: csrc/pointnet_conv_split.hip, pointnet_gram.hip); NULL = fp32 MFMA throughout. */
   float w5h_unscale;        /* 2^-e */
-  const void *w4h;          /* optional, with w5h: w4 as split-fp16 fragments (K = 64): conv4 inside conv5's staging pass */
-  float w4h_unscale;
-  const void *w5h16;        /* optional, with w5h: w5 in 16x16x32 fragment order (see t3.w3h16) */
   const void *w4th;         /* optional, with w5h: w4t [64,128] as split-fp16 fragments (see t3.w2th) */
   float w4th_unscale;
   int32_t flags;            /* GEOA3_PN_* bits; 0 = the default kernels */

@@ -175,13 +175,14 @@ def test_wide_split_operand_range(scale):
 
 
 @pytest.mark.parametrize("taps,N", [(3, 1024), (1, 1024), (3, 200), (1, 77), (3, 128)])
-def test_wide_layer_both_modes_against_float64(taps, N):
+def test_wide_layer_shipped_packing_against_float64(taps, N):
     """One 1024-wide layer (conv + bias + relu + max over points, arg-max) through geoa3_debug_wide_fwd in both
-    arithmetic modes against a float64 evaluation: values to fp32 rounding of a K = 128 * taps dot product; the
+    arithmetic modes, the split weights in the packing the library uses for the tap count (1: pack_wide_split,
+    3: pack_wide_split16), against a float64 evaluation: values to fp32 rounding of a K = 128 * taps dot product; the
     arg-max is the float64 one wherever the float64 runner-up is not within rounding noise; a non-finite activation
     poisons that instance's features with NaN in f16x2 mode (loud, never silently dropped by the max)."""
     from geoa3_amd import _lib
-    from geoa3_amd.pointnet import pack_wide_fragments, pack_wide_split
+    from geoa3_amd.pointnet import pack_wide_fragments, pack_wide_split, pack_wide_split16
     lib = _lib.load()
     B = 5
     g = torch.Generator().manual_seed(taps * 1000 + N)
@@ -196,7 +197,7 @@ def test_wide_layer_both_modes_against_float64(taps, N):
     ref_out = (ref + bias.double()).clamp_min(0)
     mag = torch.nn.functional.conv1d(X.double().abs(), W.double().abs().view(1024, taps, 128).permute(0, 2, 1),
                                      padding=taps // 2).max(dim=2).values          # bound on sum |a w|
-    Wp, (Wh, uns) = pack_wide_fragments(W, taps).cuda(), pack_wide_split(W, taps)
+    Wp, (Wh, uns) = pack_wide_fragments(W, taps).cuda(), (pack_wide_split16 if taps == 3 else pack_wide_split)(W)
     Wh, Xd, bd = Wh.cuda(), X.cuda(), bias.cuda()
     out = torch.empty(B, 1024, device="cuda")
     arg = torch.empty(B, 1024, device="cuda", dtype=torch.int32)
@@ -206,7 +207,7 @@ def test_wide_layer_both_modes_against_float64(taps, N):
     def run(split, x):
         _lib.check(lib.geoa3_debug_wide_fwd(x.data_ptr(), Wp.data_ptr(), Wh.data_ptr() if split else None, uns,
                                             bd.data_ptr(), out.data_ptr(), arg.data_ptr(), keys.data_ptr(), B, N, taps,
-                                            0, None, s), "geoa3_debug_wide_fwd")
+                                            None, s), "geoa3_debug_wide_fwd")
         return out.cpu().double(), arg.cpu().long()
 
     for split in (False, True):

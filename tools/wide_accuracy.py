@@ -52,7 +52,7 @@ def main():
 
     # one 1024-wide layer in isolation: pooled pre-activations against float64
     from geoa3_amd import _lib
-    from geoa3_amd.pointnet import pack_wide_fragments, pack_wide_split
+    from geoa3_amd.pointnet import pack_wide_fragments, pack_wide_split, pack_wide_split16
     lib = _lib.load()
     g = torch.Generator().manual_seed(5)
     for taps in (3, 1):
@@ -61,7 +61,7 @@ def main():
         W = torch.randn(1024, taps * 128, generator=g) * 0.05
         ref = torch.nn.functional.conv1d(X.double(), W.double().view(1024, taps, 128).permute(0, 2, 1),
                                          padding=taps // 2).max(dim=2).values
-        Wp, (Wh, uns) = pack_wide_fragments(W, taps).cuda(), pack_wide_split(W, taps)
+        Wp, (Wh, uns) = pack_wide_fragments(W, taps).cuda(), (pack_wide_split16 if taps == 3 else pack_wide_split)(W)
         Wh, Xd = Wh.cuda(), X.cuda()
         bias = torch.full((1024,), 1e6, device="cuda")      # keeps the relu out of the way; subtracted again below
         out = torch.empty(B, 1024, device="cuda")
@@ -71,7 +71,7 @@ def main():
         for split in (False, True):
             # bias 0: negative maxima are clipped by the relu -- compare where the reference is positive
             lib.geoa3_debug_wide_fwd(Xd.data_ptr(), Wp.data_ptr(), Wh.data_ptr() if split else None, uns,
-                                     zero.data_ptr(), out.data_ptr(), arg.data_ptr(), keys.data_ptr(), B, N, taps, 0,
+                                     zero.data_ptr(), out.data_ptr(), arg.data_ptr(), keys.data_ptr(), B, N, taps,
                                      None, torch.cuda.current_stream().cuda_stream)
             o = out.cpu().double()
             pos = ref > 0
