@@ -43,6 +43,11 @@ class AttackRunner:
         if self.w_uni != 0 and global_batch is not None and global_batch != b:
             raise ValueError("uniform_loss_weight != 0 needs the whole batch on one GPU: U is a mean over all %d "
                              "instances (this shard holds %d)" % (global_batch, b))
+        # --is_use_knn_smoothing_loss (an extension: the reference parses --knn_smoothing_loss_weight / --knn_smoothing_k /
+        # --knn_threshold_coef, main_attack.py:52-54, and never reads them): w * kNN_smoothing_loss(x, k, coef)
+        # (Lib/loss_utils.py:135-149) joins every row's constrain loss.  Per row: a sharded batch needs nothing.
+        self.w_knn = (float(_cfg(cfg, "knn_smoothing_loss_weight", 0.0))
+                      if bool(_cfg(cfg, "is_use_knn_smoothing_loss", False)) else 0.0)
         if cfg.dis_loss_type == "L2" and cfg.hd_loss_weight != 0:
             raise AssertionError("L2 distance needs hd_loss_weight == 0")  # geoA3_attack.py:140
         if cfg.optim not in ("adam", "sgd"):
@@ -167,6 +172,20 @@ class AttackRunner:
             self.knn_slab = True
             self.knn_method = int(_cfg(cfg, "knn_method", 0))   # geoa3_knn_self: 0 = by (K, N), 1 = slab, 2 = cell grid
             t["knn_scratch"] = ops.knn_self_scratch(b, ne, device)
+        if self.w_knn != 0:
+            self.ks = int(_cfg(cfg, "knn_smoothing_k", 5))
+            self.knn_coef = float(_cfg(cfg, "knn_threshold_coef", 1.10))
+            if not 1 <= self.ks < min(ne, 64):
+                raise ValueError("knn_smoothing_k must be in 1..%d" % (min(ne, 64) - 1))
+            # the curvature term's table of this iteration holds the ks + 1 nearest in its first columns
+            # (cfg.knn_smoothing_share_table = False: tests, a search of its own)
+            self.knn_share = self.use_curv and self.ks <= self.k and bool(_cfg(cfg, "knn_smoothing_share_table", True))
+            t["ks_loss"], t["ks_grad"] = z(b), z(b, 3, ne)
+            self.ks_ws = ops.reg_workspace(b, ne, self.ks, device)
+            if not self.knn_share:
+                t["ks_knn"] = [torch.zeros(b, ne, self.ks + 1, **i32) for _ in range(2)]
+                t["ks_knn_d"] = z(b, ne, self.ks + 1)
+                t["ks_scratch"] = t["knn_scratch"] if self.use_curv else ops.knn_self_scratch(b, ne, device)
         if self.native:
             bw = b * self.eval_num if self.sub else b
             nbytes = (self.lib.geoa3_pn2ssg_workspace_bytes(bw, ne) if self.ssg
@@ -218,6 +237,11 @@ class AttackRunner:
             self.knn_seeded = not self.sub
             if self.knn_seeded:
                 t["knn"][0].copy_(knn_ori)
+        if self.w_knn != 0 and not self.knn_share:   # the prior of the term's own search: the clean cloud's neighbours
+            self.ks_cur = 0
+            self.ks_seeded = not self.sub
+            if self.ks_seeded:
+                t["ks_knn"][0].copy_(ops.knn_planar(self.ori, self.ori, self.ks + 1)[1])
         cls_type = {"None": 0, "CE": 1, "Margin": 2}[cfg.cls_loss_type]
         self.state = AttackState(
             B=self.b, N=self.n, classes=self.classes, targeted=int(self.targeted), cls_loss_type=cls_type,
@@ -398,6 +422,32 @@ class AttackRunner:
                                   deterministic=self.deterministic, scratch=self.geo_scratch)
                 constrain = self.geo_out["constrain"]
             geo_on = constrain is not None
+            if self.w_knn != 0:
+                # S_b = kNN_smoothing_loss(xe)[b] and dS_b/dx on the geometry stream, then constrain_b (+)= w S_b (before the
+                # head reads it) and g_geo (+)= w dS_b/dx.  g_geo stays UN-scaled: attack_update_kernel multiplies all of it
+                # by scale_const[b] * inv_global_batch (= c_b / b, the gradient of mean_b(c_b constrain_b)) when it forms
+                # g = g_cls + (c_b / b) g_geo, so the term gets the factor of the other constraint terms there, once.
+                if self.knn_share:
+                    table, ld = (t["knn_d"], knn_adv), self.k + 1
+                else:
+                    prior, out = t["ks_knn"][self.ks_cur], t["ks_knn"][1 - self.ks_cur]
+                    check(lib.geoa3_knn_self(xe.data_ptr(), self.b, ne, self.ks + 1,
+                                             prior.data_ptr() if self.ks_seeded else None, t["ks_knn_d"].data_ptr(),
+                                             out.data_ptr(), t["ks_scratch"].data_ptr(), 0, sg), "knn_self")
+                    self.ks_seeded = True
+                    self.ks_cur = 1 - self.ks_cur
+                    table, ld = (t["ks_knn_d"], out), self.ks + 1
+                tb = (table[0].data_ptr(), table[1].data_ptr(), ld)
+                check(lib.geoa3_knn_smoothing_loss(xe.data_ptr(), self.b, ne, self.ks, self.knn_coef, *tb,
+                                                   t["ks_loss"].data_ptr(), None, self.ks_ws.data_ptr(), sg),
+                      "knn_smoothing_loss")
+                check(lib.geoa3_knn_smoothing_loss_grad(xe.data_ptr(), self.b, ne, self.ks, self.knn_coef, *tb, None,
+                                                        t["ks_grad"].data_ptr(), self.ks_ws.data_ptr(), sg),
+                      "knn_smoothing_loss_grad")
+                constrain = self.geo_out["constrain"]
+                ops.reg_fold(t["ks_loss"], t["ks_grad"], self.w_knn, self.b, ne, constrain=constrain, constrain_add=geo_on,
+                             g=t["g_geo"], g_add=geo_on, stream=sg)
+                geo_on = True
             if self.w_uni != 0:   # constrain (+)= w U before the head reads it (no other term on: constrain = w U)
                 ops.uniform_loss(xe, contract=self.uni_contract, workspace=self.uni_ws, out=(t["uni_loss"], t["uni_grad"]))
                 constrain = self.geo_out["constrain"]
@@ -502,7 +552,8 @@ class AttackRunner:
         vals = torch.stack([t["loss_n"].mean() * (self.b / float(self.global_batch)), t["cls_loss"].mean(),
                             self.geo_out["dis_loss"].mean(), self.geo_out["hd_loss"].mean(),
                             self.geo_out["curv_loss"].mean()] +
-                           ([self.t["uni_loss"]] if self.w_uni != 0 else [])).tolist()
+                           ([self.t["uni_loss"]] if self.w_uni != 0 else []) +
+                           ([self.t["ks_loss"].mean()] if self.w_knn != 0 else [])).tolist()
         info = "[{5}/{6}][{0}/{1}][{2}/{3}] \t loss: {4:6.4f}\t".format(
             search_step + 1, cfg.binary_max_steps, step + 1, cfg.iter_max_steps, vals[0], i, loader_len)
         info += "cls_loss: {0:6.4f}\t".format(vals[1])
@@ -516,6 +567,8 @@ class AttackRunner:
             info += "curv_loss : {0:6.4f}\t".format(vals[4])
         if self.w_uni != 0:
             info += "uniform : {0:6.4f}\t".format(vals[5])
+        if self.w_knn != 0:
+            info += "knn_smooth : {0:6.4f}\t".format(vals[-1])
         return info
 
     def run(self, init_offsets: Optional[Sequence[Tensor]] = None, i: int = 0, loader_len: int = 1,
@@ -567,7 +620,9 @@ class AttackRunner:
 RUNNER_CFG_FIELDS = ("attack_label", "iter_max_steps", "curv_loss_knn", "curv_loss_weight", "dis_loss_type",
                      "hd_loss_weight", "cls_loss_type", "optim", "uniform_loss_weight", "npoint", "is_partial_var",
                      "knn_range", "is_subsample_opt", "eval_num", "is_pre_jitter_input", "is_pro_grad",
-                     "brute_force_nn1", "classes", "deterministic", "late_join", "knn_method")
+                     "brute_force_nn1", "classes", "deterministic", "late_join", "knn_method",
+                     "is_use_knn_smoothing_loss", "knn_smoothing_loss_weight", "knn_smoothing_k", "knn_threshold_coef",
+                     "knn_smoothing_share_table")
 
 
 def unpack_input(input_data, targeted: bool):

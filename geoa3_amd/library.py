@@ -15,6 +15,7 @@ differentiates through it, a registered autograd formula.  `geoa3_amd.ops.knn_po
     geoa3::point_loss      chamfer / pseudo-chamfer / hausdorff / l2 with autograd    Lib/loss_utils.py:25-50
     geoa3::kappa_adv       _get_kappa_adv with autograd                               Lib/loss_utils.py:64-82
     geoa3::uniform_loss    uniform_loss (one scalar for the batch) with autograd      Lib/loss_utils.py:151-189
+    geoa3::knn_smoothing_loss / repulsion_loss / displacement_loss / corresponding_normal_loss  with autograd  Lib/loss_utils.py:99-149
     geoa3::pointnet_forward / _backward   PointNet.forward (eval) and its input gradient   Model/PointNet.py:132-160
 """
 from __future__ import annotations
@@ -233,6 +234,158 @@ def _uniform_backward(ctx, g, _gg):
 
 
 uniform_loss.register_autograd(_uniform_backward, setup_context=_uniform_setup)
+
+# ------------------------------------------------------------------------------------------------ neighbour regularisers
+# Each forward returns the K-NN table it used beside the value, so that the registered backward (itself an op: a traced
+# backward graph holds it) differentiates THAT selection, as autograd does through the reference's topk / knn_points.
+@custom_op("geoa3::knn_smoothing_loss", mutates_args=(), device_types="cuda")
+def knn_smoothing_loss(adv_pc: Tensor, k: int, threshold_coef: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """kNN_smoothing_loss on adv_pc [b,3,n] -> (loss [b], mask [b,n] uint8, knn dists [b,n,k+1], knn idx int32)."""
+    x = _planar(adv_pc)
+    d, i = ops.knn_self_planar(x, k + 1)
+    loss, cond = ops.knn_smoothing_loss(x, k, threshold_coef, knn=(d, i), want_cond=True)
+    return loss, cond, d, i
+
+
+@knn_smoothing_loss.register_fake
+def _(adv_pc, k, threshold_coef):
+    b, _, n = adv_pc.shape
+    return (adv_pc.new_empty(b, dtype=_f32), adv_pc.new_empty(b, n, dtype=torch.uint8),
+            adv_pc.new_empty(b, n, k + 1, dtype=_f32), adv_pc.new_empty(b, n, k + 1, dtype=_i32))
+
+
+@custom_op("geoa3::knn_smoothing_loss_grad", mutates_args=(), device_types="cuda")
+def knn_smoothing_loss_grad(adv_pc: Tensor, knn_d: Tensor, knn_i: Tensor, g: Tensor, k: int, threshold_coef: float) -> Tensor:
+    return ops.knn_smoothing_loss_grad(_planar(adv_pc), k, threshold_coef, g=g.contiguous().float(),
+                                       knn=(knn_d.contiguous(), knn_i.contiguous()))
+
+
+@knn_smoothing_loss_grad.register_fake
+def _(adv_pc, knn_d, knn_i, g, k, threshold_coef):
+    return adv_pc.new_empty(adv_pc.shape, dtype=_f32)
+
+
+def _smooth_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], output[2], output[3])
+    ctx.k, ctx.coef = inputs[1], inputs[2]
+
+
+def _smooth_backward(ctx, g, _gc, _gd, _gi):
+    x, d, i = ctx.saved_tensors
+    return torch.ops.geoa3.knn_smoothing_loss_grad(x, d, i, g, ctx.k, ctx.coef), None, None
+
+
+knn_smoothing_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
+
+
+@custom_op("geoa3::repulsion_loss", mutates_args=(), device_types="cuda")
+def repulsion_loss(pc: Tensor, k: int, h: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """repulsion_loss on pc [b,3,n] -> (out [b,n], knn dists [b,n,k+1], knn idx int32)."""
+    x = _planar(pc)
+    d, i = ops.knn_self_planar(x, k + 1)
+    return ops.repulsion_loss(x, k, h, knn=(d, i)), d, i
+
+
+@repulsion_loss.register_fake
+def _(pc, k, h):
+    b, _, n = pc.shape
+    return (pc.new_empty(b, n, dtype=_f32), pc.new_empty(b, n, k + 1, dtype=_f32), pc.new_empty(b, n, k + 1, dtype=_i32))
+
+
+@custom_op("geoa3::repulsion_loss_grad", mutates_args=(), device_types="cuda")
+def repulsion_loss_grad(pc: Tensor, knn_d: Tensor, knn_i: Tensor, g: Tensor, k: int, h: float) -> Tensor:
+    return ops.repulsion_loss_grad(_planar(pc), k, h, g=g.contiguous().float(), knn=(knn_d.contiguous(), knn_i.contiguous()))
+
+
+@repulsion_loss_grad.register_fake
+def _(pc, knn_d, knn_i, g, k, h):
+    return pc.new_empty(pc.shape, dtype=_f32)
+
+
+def _repulse_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], output[1], output[2])
+    ctx.k, ctx.h = inputs[1], inputs[2]
+
+
+def _repulse_backward(ctx, g, _gd, _gi):
+    x, d, i = ctx.saved_tensors
+    return torch.ops.geoa3.repulsion_loss_grad(x, d, i, g, ctx.k, ctx.h), None, None
+
+
+repulsion_loss.register_autograd(_repulse_backward, setup_context=_repulse_setup)
+
+
+@custom_op("geoa3::displacement_loss", mutates_args=(), device_types="cuda")
+def displacement_loss(adv_pc: Tensor, ori_pc: Tensor, k: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """displacement_loss on adv_pc, ori_pc [b,3,n] -> (out [b,n], knn dists / idx [b,n,k+1] of ORI)."""
+    adv, ori = _planar(adv_pc), _planar(ori_pc)
+    d, i = ops.knn_self_planar(ori, k + 1)
+    return ops.displacement_loss(adv, ori, k, knn=(d, i)), d, i
+
+
+@displacement_loss.register_fake
+def _(adv_pc, ori_pc, k):
+    b, _, n = adv_pc.shape
+    return (adv_pc.new_empty(b, n, dtype=_f32), adv_pc.new_empty(b, n, k + 1, dtype=_f32),
+            adv_pc.new_empty(b, n, k + 1, dtype=_i32))
+
+
+@custom_op("geoa3::displacement_loss_grad", mutates_args=(), device_types="cuda")
+def displacement_loss_grad(adv_pc: Tensor, ori_pc: Tensor, knn_d: Tensor, knn_i: Tensor, g: Tensor, k: int) -> Tensor:
+    return ops.displacement_loss_grad(_planar(adv_pc), _planar(ori_pc), k, g=g.contiguous().float(),
+                                      knn=(knn_d.contiguous(), knn_i.contiguous()))
+
+
+@displacement_loss_grad.register_fake
+def _(adv_pc, ori_pc, knn_d, knn_i, g, k):
+    return adv_pc.new_empty(adv_pc.shape, dtype=_f32)
+
+
+def _displace_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[1], output[2])
+    ctx.k = inputs[2]
+
+
+def _displace_backward(ctx, g, _gd, _gi):
+    adv, ori, d, i = ctx.saved_tensors
+    return torch.ops.geoa3.displacement_loss_grad(adv, ori, d, i, g, ctx.k), None, None
+
+
+displacement_loss.register_autograd(_displace_backward, setup_context=_displace_setup)
+
+
+@custom_op("geoa3::corresponding_normal_loss", mutates_args=(), device_types="cuda")
+def corresponding_normal_loss(adv_pc: Tensor, normal: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """corresponding_normal_loss on adv_pc, normal [b,3,n] -> (out [b,n], knn idx int32 [b,n,k+1] of adv)."""
+    return ops.corresponding_normal_loss(_planar(adv_pc), _planar(normal), k, want_knn=True)
+
+
+@corresponding_normal_loss.register_fake
+def _(adv_pc, normal, k):
+    b, _, n = adv_pc.shape
+    return adv_pc.new_empty(b, n, dtype=_f32), adv_pc.new_empty(b, n, k + 1, dtype=_i32)
+
+
+@custom_op("geoa3::corresponding_normal_loss_grad", mutates_args=(), device_types="cuda")
+def corresponding_normal_loss_grad(adv_pc: Tensor, normal: Tensor, knn_i: Tensor, g: Tensor) -> Tensor:
+    return ops.corresponding_normal_loss_grad(_planar(adv_pc), _planar(normal), knn_i.contiguous(), g.contiguous().float())
+
+
+@corresponding_normal_loss_grad.register_fake
+def _(adv_pc, normal, knn_i, g):
+    return adv_pc.new_empty(adv_pc.shape, dtype=_f32)
+
+
+def _cnl_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[1])
+
+
+def _cnl_backward(ctx, g, _gi):
+    adv, nrm, i = ctx.saved_tensors
+    return torch.ops.geoa3.corresponding_normal_loss_grad(adv, nrm, i, g), None, None
+
+
+corresponding_normal_loss.register_autograd(_cnl_backward, setup_context=_cnl_setup)
 
 # ------------------------------------------------------------------------------------------------ the victim
 import weakref

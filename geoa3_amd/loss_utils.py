@@ -8,6 +8,11 @@ _forward_step composition (Attacker/geoA3_attack.py:131-166) and swap only the i
     Lib/loss_utils.py:28-35   chamfer_loss          Lib/loss_utils.py:64-82   _get_kappa_adv
     Lib/loss_utils.py:37-43   pseudo_chamfer_loss   Lib/loss_utils.py:84-97   curvature_loss
     Lib/loss_utils.py:45-50   hausdorff_loss        Lib/loss_utils.py:151-189 uniform_loss
+    Lib/loss_utils.py:99-107  displacement_loss     Lib/loss_utils.py:109-117 corresponding_normal_loss
+    Lib/loss_utils.py:119-123 repulsion_loss        Lib/loss_utils.py:135-149 kNN_smoothing_loss
+
+Not mirrored: distance_kmean_loss (Lib/loss_utils.py:125-133).  It ranks neighbours by sqrt(sum((delta + 1e-12)^2)), another
+distance arithmetic than the pinned K-NN's, its gradient is two-hop, and nothing in the reference calls it.
 """
 from __future__ import annotations
 
@@ -66,3 +71,25 @@ def uniform_loss(adv_pc: Tensor, percentages=[0.004, 0.006, 0.008, 0.010, 0.012]
     x = adv_pc if adv_pc.size(1) == 3 else adv_pc.permute(0, 2, 1)
     return torch.ops.geoa3.uniform_loss(x, [float(p) for p in percentages], float(radius), int(k),
                                         -1 if contract is None else int(bool(contract)))[0]
+
+
+# The neighbour-based regularisers (csrc/geom_reg.hip): the reference's names, argument names and defaults; [b,3,n] in, the
+# reference's output shape out, differentiable w.r.t. adv_pc / pc only.
+def displacement_loss(adv_pc: Tensor, ori_pc: Tensor, k: int = 16) -> Tensor:
+    """-> [b,n]; the neighbours are ori_pc's and carry no gradient."""
+    return torch.ops.geoa3.displacement_loss(adv_pc, ori_pc, int(k))[0]
+
+
+def corresponding_normal_loss(adv_pc: Tensor, normal: Tensor, k: int = 2) -> Tensor:
+    """-> [b,n]"""
+    return torch.ops.geoa3.corresponding_normal_loss(adv_pc, normal, int(k))[0]
+
+
+def repulsion_loss(pc: Tensor, k: int = 4, h: float = 0.03) -> Tensor:
+    """-> [b,n]"""
+    return torch.ops.geoa3.repulsion_loss(pc, int(k), float(h))[0]
+
+
+def kNN_smoothing_loss(adv_pc: Tensor, k: int, threshold_coef: float = 1.05) -> Tensor:
+    """-> [b]; the mask s_i > mean + threshold_coef * std carries no gradient."""
+    return torch.ops.geoa3.knn_smoothing_loss(adv_pc, int(k), float(threshold_coef))[0]

@@ -203,6 +203,154 @@ def uniform_fold(loss: Tensor, grad: Optional[Tensor], scale_const: Optional[Ten
 
 
 # ---------------------------------------------------------------------------------------------
+# Neighbour-based regularisers (csrc/geom_reg.hip): kNN_smoothing_loss / repulsion_loss / displacement_loss /
+# corresponding_normal_loss of Lib/loss_utils.py:99-149.  `knn` = (dists, idx) [B,N,K >= k+1] of geoa3_knn_self on the
+# cloud the table belongs to (displacement_loss: ori); None: the entry point computes it into `workspace`.
+# ---------------------------------------------------------------------------------------------
+def reg_workspace(B: int, N: int, k: int, device) -> Tensor:
+    """Workspace of the geoa3_*_loss(_grad) entry points of csrc/geom_reg.hip for [B,3,N] clouds."""
+    return torch.empty(max(int(_lib.load().geoa3_reg_workspace_bytes(B, N, int(k))), 256), dtype=torch.uint8, device=device)
+
+
+def _reg_table(knn, B: int, N: int, k: int):
+    if knn is None:
+        return None, None, 0
+    d, i = knn
+    if d.dim() != 3 or tuple(d.shape) != tuple(i.shape) or d.shape[0] != B or d.shape[1] != N or d.shape[2] < k + 1:
+        raise _lib.Geoa3Error("knn must be (dists, idx) of shape [%d,%d,K >= %d]" % (B, N, k + 1))
+    return _p(d, torch.float32), _p(i, torch.int32), int(d.shape[2])
+
+
+def _reg_ws(workspace, B, N, k, device):
+    return workspace if workspace is not None else reg_workspace(B, N, k, device)
+
+
+def knn_smoothing_loss(pc: Tensor, k: int, threshold_coef: float = 1.05, knn=None, workspace: Optional[Tensor] = None,
+                       out=None, want_cond: bool = False):
+    """kNN_smoothing_loss (Lib/loss_utils.py:135-149) on pc [B,3,N] -> loss [B] (with want_cond: also the mask [B,N] uint8)."""
+    B, _, N = pc.shape
+    loss = out if out is not None else torch.empty(B, device=pc.device, dtype=torch.float32)
+    cond = torch.empty(B, N, device=pc.device, dtype=torch.uint8) if want_cond else None
+    d, i, ld = _reg_table(knn, B, N, int(k))
+    check(_lib.load().geoa3_knn_smoothing_loss(_p(pc, torch.float32), B, N, int(k), float(threshold_coef), d, i, ld,
+                                               _p(loss, torch.float32), _p(cond), _p(_reg_ws(workspace, B, N, k, pc.device)),
+                                               _stream()), "geoa3_knn_smoothing_loss")
+    return (loss, cond) if want_cond else loss
+
+
+def knn_smoothing_loss_grad(pc: Tensor, k: int, threshold_coef: float = 1.05, g: Optional[Tensor] = None, knn=None,
+                            workspace: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """d (sum_b g_b loss_b) / d pc [B,3,N] (g [B]; None = ones)."""
+    B, _, N = pc.shape
+    grad = out if out is not None else torch.empty(B, 3, N, device=pc.device, dtype=torch.float32)
+    d, i, ld = _reg_table(knn, B, N, int(k))
+    check(_lib.load().geoa3_knn_smoothing_loss_grad(_p(pc, torch.float32), B, N, int(k), float(threshold_coef), d, i, ld,
+                                                    _p(g, torch.float32), _p(grad, torch.float32),
+                                                    _p(_reg_ws(workspace, B, N, k, pc.device)), _stream()),
+          "geoa3_knn_smoothing_loss_grad")
+    return grad
+
+
+def repulsion_loss(pc: Tensor, k: int = 4, h: float = 0.03, knn=None, workspace: Optional[Tensor] = None,
+                   out: Optional[Tensor] = None) -> Tensor:
+    """repulsion_loss (Lib/loss_utils.py:119-123) on pc [B,3,N] -> [B,N]."""
+    B, _, N = pc.shape
+    o = out if out is not None else torch.empty(B, N, device=pc.device, dtype=torch.float32)
+    d, i, ld = _reg_table(knn, B, N, int(k))
+    check(_lib.load().geoa3_repulsion_loss(_p(pc, torch.float32), B, N, int(k), float(h), d, i, ld, _p(o, torch.float32),
+                                           _p(_reg_ws(workspace, B, N, k, pc.device)), _stream()), "geoa3_repulsion_loss")
+    return o
+
+
+def repulsion_loss_grad(pc: Tensor, k: int = 4, h: float = 0.03, g: Optional[Tensor] = None, knn=None,
+                        workspace: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """d (sum g . out) / d pc [B,3,N] (g [B,N]; None = ones)."""
+    B, _, N = pc.shape
+    grad = out if out is not None else torch.empty(B, 3, N, device=pc.device, dtype=torch.float32)
+    d, i, ld = _reg_table(knn, B, N, int(k))
+    check(_lib.load().geoa3_repulsion_loss_grad(_p(pc, torch.float32), B, N, int(k), float(h), d, i, ld,
+                                                _p(g, torch.float32), _p(grad, torch.float32),
+                                                _p(_reg_ws(workspace, B, N, k, pc.device)), _stream()),
+          "geoa3_repulsion_loss_grad")
+    return grad
+
+
+def displacement_loss(adv: Tensor, ori: Tensor, k: int = 16, knn=None, workspace: Optional[Tensor] = None,
+                      out: Optional[Tensor] = None) -> Tensor:
+    """displacement_loss (Lib/loss_utils.py:99-107) on adv, ori [B,3,N] -> [B,N]; knn: the table of ORI."""
+    B, _, N = adv.shape
+    if tuple(ori.shape) != (B, 3, N):
+        raise _lib.Geoa3Error("displacement_loss: adv and ori must have the same shape")
+    o = out if out is not None else torch.empty(B, N, device=adv.device, dtype=torch.float32)
+    d, i, ld = _reg_table(knn, B, N, int(k))
+    check(_lib.load().geoa3_displacement_loss(_p(adv, torch.float32), _p(ori, torch.float32), B, N, int(k), d, i, ld,
+                                              _p(o, torch.float32), _p(_reg_ws(workspace, B, N, k, adv.device)), _stream()),
+          "geoa3_displacement_loss")
+    return o
+
+
+def displacement_loss_grad(adv: Tensor, ori: Tensor, k: int = 16, g: Optional[Tensor] = None, knn=None,
+                           workspace: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """d (sum g . out) / d adv [B,3,N] (g [B,N]; None = ones)."""
+    B, _, N = adv.shape
+    if tuple(ori.shape) != (B, 3, N):
+        raise _lib.Geoa3Error("displacement_loss: adv and ori must have the same shape")
+    grad = out if out is not None else torch.empty(B, 3, N, device=adv.device, dtype=torch.float32)
+    d, i, ld = _reg_table(knn, B, N, int(k))
+    check(_lib.load().geoa3_displacement_loss_grad(_p(adv, torch.float32), _p(ori, torch.float32), B, N, int(k), d, i, ld,
+                                                   _p(g, torch.float32), _p(grad, torch.float32),
+                                                   _p(_reg_ws(workspace, B, N, k, adv.device)), _stream()),
+          "geoa3_displacement_loss_grad")
+    return grad
+
+
+def _reg_check(B: int, N: int, k: int) -> None:
+    if k < 1 or N < k + 1:
+        raise _lib.Geoa3Error("corresponding_normal_loss failed: invalid argument (k = %d, N = %d)" % (k, N))
+    if k + 1 > 64 or N > 8192:
+        raise _lib.Geoa3Error("corresponding_normal_loss failed: not supported (k + 1 <= 64, N <= 8192)")
+
+
+def _instance_bad(pc: Tensor) -> Tensor:
+    return ~torch.isfinite(pc).flatten(1).all(1)
+
+
+def corresponding_normal_loss(adv: Tensor, normal: Tensor, k: int = 2, knn=None, want_knn: bool = False):
+    """corresponding_normal_loss (Lib/loss_utils.py:109-117) on adv, normal [B,3,N] -> [B,N]: geoa3_kappa on adv's own
+    K-NN with the point's own normal.  want_knn: also the index table [B,N,k+1] the backward needs."""
+    B, _, N = adv.shape
+    _reg_check(B, N, int(k))
+    idx = knn[1][:, :, :k + 1].contiguous() if knn is not None else knn_self_planar(adv, int(k) + 1)[1]
+    # a point with a non-finite coordinate has no neighbours (index -1): the whole instance is NaN, as in the kernels of
+    # csrc/geom_reg.hip, and the table stays inside the cloud
+    idx = idx.clamp(0, N - 1)
+    out = kappa(adv, normal, idx)
+    out = torch.where(_instance_bad(adv).view(B, 1), out.new_full((), float("nan")), out)
+    return (out, idx) if want_knn else out
+
+
+def corresponding_normal_loss_grad(adv: Tensor, normal: Tensor, knn_idx: Tensor, g: Optional[Tensor] = None) -> Tensor:
+    """d (sum g . out) / d adv [B,3,N]: the dkappa path of geoa3_geo_loss_grad with the identity as nearest-point index."""
+    B, _, N = adv.shape
+    k = int(knn_idx.shape[2]) - 1
+    _reg_check(B, N, k)
+    ident = torch.arange(N, device=adv.device, dtype=torch.int32).unsqueeze(0).expand(B, N).contiguous()
+    if g is None:
+        g = torch.ones(B, N, device=adv.device, dtype=torch.float32)
+    o = geo_loss_grad(adv, adv, normal_ori=normal, i_ao=ident, knn_adv=knn_idx, dkappa=g.contiguous(), k=k, dis_type=0,
+                      w_dis=0.0, w_hd=0.0, w_curv=0.0, deterministic=True)
+    return torch.where(_instance_bad(adv).view(B, 1, 1), o["grad"].new_full((), float("nan")), o["grad"])
+
+
+def reg_fold(loss: Optional[Tensor], grad: Optional[Tensor], w: float, B: int, N: int, constrain: Optional[Tensor] = None,
+             constrain_add: bool = False, g: Optional[Tensor] = None, g_add: bool = False,
+             stream: Optional[int] = None) -> None:
+    """geoa3_reg_fold: constrain (+)= w loss [B]; g (+)= w grad [B,3,N]."""
+    check(_lib.load().geoa3_reg_fold(_p(loss), _p(grad), float(w), B, N, _p(constrain), int(constrain_add), _p(g),
+                                     int(g_add), _stream() if stream is None else stream), "geoa3_reg_fold")
+
+
+# ---------------------------------------------------------------------------------------------
 # Operator-level mirror of pytorch3d.ops (SURVEY 8b-1): [b,n,3] point-major arguments, int64 idx,
 # differentiable through `dists`.
 # ---------------------------------------------------------------------------------------------

@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 601
+#define GEOA3_ABI_VERSION 602
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -532,6 +532,48 @@ int geoa3_uniform_loss(const float* pc, int B, int N, const double* percentages,
  * mean_b(scale_const[b] * w * U), which couples the rows of the batch. */
 int geoa3_uniform_fold(const float* loss, const float* grad, const float* scale_const, float w, int B, int N,
                        float* constrain, int constrain_add, float* g, int g_add, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Neighbour-based regularisers of Lib/loss_utils.py: functions of a self K-NN table, per row of the batch.
+ * The table: (knn_d, knn_i) [B,N,knn_ld] as geoa3_knn_self(cloud, K >= k + 1) writes it (knn_ld = its K; 0 means k + 1;
+ * the first k + 1 columns are used, column 0 is dropped as the reference's [:, :, 1:]), both given or both NULL.
+ * NULL: the entry point runs geoa3_knn_self(cloud, k + 1) itself into `workspace` (geoa3_reg_workspace_bytes(B, N, k)
+ * bytes, 256-byte aligned; also required for clouds of more than ~4200 points, whose gradient sums do not fit in LDS).
+ * Every *_grad entry point writes grad [B,3,N] = d (sum g . out) / d cloud; g = NULL means ones.  Gradient sums are
+ * order-free 64-bit fixed point at the instance's own scale: repeated calls are bit identical, and a row does not depend
+ * on the rest of the batch.  Supported: 2 <= k + 1 <= GEOA3_KNN_MAX_K, k + 1 <= N <= 8192 (GEOA3_EINVAL /
+ * GEOA3_ENOSUPPORT otherwise).  A non-finite coordinate makes every output of its instance NaN.
+ * ------------------------------------------------------------------------------------------ */
+int64_t geoa3_reg_workspace_bytes(int B, int N, int k);
+/* kNN_smoothing_loss, Lib/loss_utils.py:135-149 (the outlier term of the kNN-attack baseline; both arguments of its
+ * knn_points are adv_pc): s_i = mean_m d[i,m], thr = mean_i s + coef * std_i s (unbiased), cond[b,i] = s_i > thr
+ * ([B,N] bytes, optional), loss[b] = (1/N) sum_i s_i cond_i.  Gradient (g [B]): cond carries none; every kept pair
+ * (i, j) adds g_b / (N k) * 2 (x_i - x_j) to point i and subtracts it from point j. */
+int geoa3_knn_smoothing_loss(const float* pc, int B, int N, int k, float coef, const float* knn_d, const int32_t* knn_i,
+                             int knn_ld, float* loss, uint8_t* cond, void* workspace, void* stream);
+int geoa3_knn_smoothing_loss_grad(const float* pc, int B, int N, int k, float coef, const float* knn_d,
+                                  const int32_t* knn_i, int knn_ld, const float* g, float* grad, void* workspace,
+                                  void* stream);
+/* repulsion_loss, Lib/loss_utils.py:119-123: out[b,i] = -mean_m d exp(-d^2 / h^2), d the SQUARED distance, squared again
+ * inside the exponent as the reference writes it.  Gradient (g [B,N]): pair coefficient
+ * -(1/k) exp(-d^2/h^2) (1 - 2 d^2/h^2) g_i on 2 (x_i - x_j). */
+int geoa3_repulsion_loss(const float* pc, int B, int N, int k, float h, const float* knn_d, const int32_t* knn_i,
+                         int knn_ld, float* out, void* workspace, void* stream);
+int geoa3_repulsion_loss_grad(const float* pc, int B, int N, int k, float h, const float* knn_d, const int32_t* knn_i,
+                              int knn_ld, const float* g, float* grad, void* workspace, void* stream);
+/* displacement_loss, Lib/loss_utils.py:99-107: the table is taken on ORI and carries no gradient; theta_i =
+ * |adv_i - ori_i|^2, out[b,i] = mean_m (theta_j - theta_i)^2.  Gradient (g [B,N]) w.r.t. adv only, through theta. */
+int geoa3_displacement_loss(const float* adv, const float* ori, int B, int N, int k, const float* knn_d,
+                            const int32_t* knn_i, int knn_ld, float* out, void* workspace, void* stream);
+int geoa3_displacement_loss_grad(const float* adv, const float* ori, int B, int N, int k, const float* knn_d,
+                                 const int32_t* knn_i, int knn_ld, const float* g, float* grad, void* workspace,
+                                 void* stream);
+/* (corresponding_normal_loss, Lib/loss_utils.py:109-117, is geoa3_knn_self + geoa3_kappa with nn_idx = NULL; its gradient
+ * is the dkappa path of geoa3_geo_loss_grad with the identity as i_ao.) */
+/* A per-row term S [B] with gradient dS [B,3,N] joins the attack's constrain loss (--is_use_knn_smoothing_loss):
+ * constrain [B] (optional) = (constrain_add ? constrain : 0) + w * loss;  g [B,3,N] (optional) = (g_add ? g : 0) + w * grad. */
+int geoa3_reg_fold(const float* loss, const float* grad, float w, int B, int N, float* constrain, int constrain_add,
+                   float* g, int g_add, void* stream);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,9 @@ def build_parser() -> argparse.ArgumentParser:
     # ------------extensions (not in the reference)
     p.add_argument("--synthetic", action="store_true", default=False,
                    help="fall back to seeded synthetic data / weights when the files are missing")
+    p.add_argument("--is_use_knn_smoothing_loss", action="store_true", default=False,
+                   help="add knn_smoothing_loss_weight * kNN_smoothing_loss(knn_smoothing_k, knn_threshold_coef) to the "
+                        "constrain loss (the reference parses the three flags and never reads them)")
     p.add_argument("--out_root", default="Exps", type=str, help="root of the output tree (reference: Exps)")
     p.add_argument("--quiet", action="store_true", default=False)
     p.add_argument("--synthetic_npoint", type=int, default=0,
@@ -108,6 +111,9 @@ def saved_dir_name(cfg) -> str:
             (cfg.is_use_lr_scheduler, "_LRExp"),
             (cfg.is_pro_grad, "_ProGrad" + ("RO" if cfg.is_real_offset else "")),
             (cfg.cc_linf != 0, "_cclinf" + str(cfg.cc_linf)),
+            (getattr(cfg, "is_use_knn_smoothing_loss", False),
+             "_kNNSmooth" + str(cfg.knn_smoothing_loss_weight) + "_k" + str(cfg.knn_smoothing_k) + "_coef" +
+             str(cfg.knn_threshold_coef)),
         ]
         for cond, suffix in optional:
             if cond:
