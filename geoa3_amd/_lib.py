@@ -147,6 +147,13 @@ SIGNATURES = {
     "geoa3_debug_grid_nn1_pair": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp]),
     "geoa3_debug_fc": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "geoa3_debug_conv_cm": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "geoa3_debug_wide_bwd_conv": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int,
+                                            C.c_int, C.c_int, vp]),
+    "geoa3_debug_gram64": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_debug_conv_bwd_chain": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int,
+                                             C.c_int, vp]),
+    "geoa3_debug_fc_ex": (C.c_int, [vp, C.c_int, C.c_int64, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp, C.c_int,
+                                    C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_profile_enable": (C.c_int, [C.c_int]),
     "geoa3_profile_select": (C.c_int, [C.c_uint]),
     "geoa3_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int]),
@@ -157,7 +164,7 @@ _lib = None
 
 ENOSUPPORT = -3   # GEOA3_ENOSUPPORT
 PN2_CONTRACT = 1   # GEOA3_PN2_CONTRACT
-ABI_VERSION = 602  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
+ABI_VERSION = 603  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
 
 
 class Geoa3Error(RuntimeError):

@@ -449,3 +449,63 @@ extern "C" int geoa3_pointnet_backward(const geoa3_pointnet_weights* pw, const f
   TRY(tnet_bwd(p.t3, w.gT3, nullptr, nullptr, x, w.a2, w.m_a2, w.p3, w.i3, w.tf4, w.tf5, w, dx, B, N, s, w.hl3, w.ho3));
   return GEOA3_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// Single kernels of the backward in isolation (geoa3_hip_debug.h; tests/test_gpu_pointnet_bwd.py): each entry fills the
+// args struct the way geoa3_pointnet_backward does and calls the kernel's launcher -- nothing else.
+// ------------------------------------------------------------------------------------------
+extern "C" int geoa3_debug_wide_bwd_conv(const float* g, const int32_t* arg, const float* W, const void* Zmask,
+                                         const float* W2t, const void* W2th, float w2th_unscale, const void* Zmask2,
+                                         float* dY, const float* x3, const float* w1, const float* b1, float* dx3,
+                                         const int32_t* hits, const int32_t* hoff, int B, int N, int taps, void* stream) {
+  if (!g || !arg || !W || B <= 0 || N <= 0) return GEOA3_EINVAL;
+  WideBwdArgs a{};
+  a.g = g; a.arg = arg; a.W = W;
+  a.Zmask = static_cast<const unsigned long long*>(Zmask);
+  a.W2t = W2t; a.W2th = W2th; a.w2th_unscale = w2th_unscale;
+  a.Zmask2 = static_cast<const unsigned long long*>(Zmask2);
+  a.dY = dY; a.sYb = (long)64 * N; a.ldY = N;
+  a.x3 = x3; a.w1 = w1; a.b1 = b1; a.dx3 = dx3;
+  a.hits = hits; a.hoff = hoff;
+  a.Co = 1024; a.N = N; a.B = B; a.taps = taps;
+  return launch_wide_bwd_conv(a, geoa3_stream(stream));
+}
+
+extern "C" int geoa3_debug_gram64(const float* A, const float* G, int B, int N, float* P, float* scratch, void* stream) {
+  if (!A || !G || !P || B <= 0 || N <= 0) return GEOA3_EINVAL;
+  return launch_gram64(A, G, B, N, P, scratch, geoa3_stream(stream));
+}
+
+extern "C" int geoa3_debug_conv_bwd_chain(const float* Xa, const float* Wa, int64_t sWa, const float* Xb, const float* Wb,
+                                          const void* Zmask, const float* W2t, const float* x3, const float* T3,
+                                          const float* w1, const float* b1, float* dx, float* dTpart, float* dT, int B, int N,
+                                          void* stream) {
+  if (!dTpart || !dT) return GEOA3_EINVAL;
+  ConvBwdChainArgs a{};
+  a.Xa = Xa; a.Wa = Wa; a.sWa = (long)sWa;
+  a.Xb = Xb; a.Wb = Wb;
+  a.Zmask = static_cast<const unsigned long long*>(Zmask);
+  a.W2t = W2t;
+  a.x3 = x3; a.T3 = T3; a.w1 = w1; a.b1 = b1;
+  a.dx = dx; a.dTpart = dTpart;
+  a.N = N; a.B = B;
+  hipStream_t s = geoa3_stream(stream);
+  TRY(launch_conv_bwd_chain(a, s));
+  return launch_reduce_dT(dTpart, (N + 255) / 256, dT, B, s);
+}
+
+extern "C" int geoa3_debug_fc_ex(const float* X, int ldX, int64_t sXb, const float* W, int ldW, int64_t sWb,
+                                 const float* bias, const float* Z, int ldZ, float* Y, int ldY, int64_t sYb, int M, int Nout,
+                                 int K, int batch, int relu, int ksplit, float* kscratch, void* stream) {
+  if (!X || !W || !Y || M <= 0 || Nout <= 0 || K <= 0) return GEOA3_EINVAL;
+  FcArgs a{};
+  a.X = X; a.ldX = ldX; a.sXb = (long)sXb;
+  a.W = W; a.ldW = ldW; a.sWb = (long)sWb;
+  a.bias = bias;
+  a.Z = Z; a.ldZ = ldZ;
+  a.Y = Y; a.ldY = ldY; a.sYb = (long)sYb;
+  a.M = M; a.Nout = Nout; a.K = K; a.batch = batch; a.relu = relu;
+  a.ksplit = ksplit & 0xff; a.tile = ksplit >> 8;   // as geoa3_debug_fc: (tile << 8) | waves, 0 = the shipped choice
+  a.kscratch = kscratch;
+  return launch_fc(a, geoa3_stream(stream));
+}

@@ -47,6 +47,48 @@ int geoa3_debug_fc(const float* X, const float* W, const float* bias, float* Y, 
 int geoa3_debug_conv_cm(const float* X, const float* W, const float* bias, const float* Z, float* Y, int B, int N, int K,
                         int Co, int relu, int split /* 1: split-fp16 operands */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The kernels of geoa3_pointnet_backward one at a time (tests/test_gpu_pointnet_bwd.py).  Each entry fills the launch
+ * arguments the way the backward does and starts the kernel(s); gate bit masks are [B][ceil(N/64)][C] 64-bit words, bit j
+ * of word (w, row) = column 64 w + j (bits of columns >= N are ignored).
+ *
+ * Hit lists (hits [B][1024 taps], hoff [B][N + 1]; written by the forward's finalize pass into the workspace buffers
+ * hl3 / ho3, hlq / hoq, hl5 / ho5).  An entry is (co * taps + tap) | (m << 16), filed under the column m = arg[co] + tap
+ * - taps / 2 the tap's gradient lands on; a tap with m outside [0, N) has no entry.  Entries are sorted by column and,
+ * inside a column, by (co / 64, tap, co); hoff[m] is the index of column m's first entry, hoff[N] the instance's entry
+ * count (slots behind it are not written).  A channel whose pooled output is not positive (relu-dead: its upstream
+ * gradient is zero) has no entries; a NaN output counts as live.  The backward expects g == 0 on every channel that is
+ * not listed; a listed channel with g == 0 adds zeros but moves the waves' share boundaries, so the sums may be added
+ * in another order than without the lists.
+ * ------------------------------------------------------------------------------------------ */
+/* The sparse arg-max backward of a 1024-wide layer and the gated 128 -> 64 layer behind it in one kernel
+ * (pointnet_wide_bwdconv.hip): g [B,1024], arg [B,1024], W [1024, taps*128], Zmask = gate bits of the 128-channel
+ * activation, W2t [64,128] with W2th = pack_wide_split(W2t) and w2th_unscale.  Either Zmask2 (gate bits of the 64-channel
+ * activation) and dY [B,64,N] (written), or -- first-layer form, taps = 1 -- x3 [B,3,N], w1 [64,3], b1 [64] and dx3 [B,3,N]
+ * (added into; Zmask2 / dY unused).  hits / hoff: both or neither (NULL: every workgroup builds its tile's lists from g /
+ * arg). */
+int geoa3_debug_wide_bwd_conv(const float* g, const int32_t* arg, const float* W, const void* Zmask, const float* W2t,
+                              const void* W2th, float w2th_unscale, const void* Zmask2, float* dY, const float* x3,
+                              const float* w1, const float* b1, float* dx3, const int32_t* hits, const int32_t* hoff, int B,
+                              int N, int taps, void* stream);
+/* P[b][i][o] = sum_n A[b][i][n] G[b][o][n], A and G [B,64,N], P [B,64,64] (pointnet_gram.hip).  scratch: B * parts * 4096
+ * floats, parts = 8 / 4 / 1 from 8 / 4 / fewer 128-column chunks on; NULL = one part. */
+int geoa3_debug_gram64(const float* A, const float* G, int B, int N, float* P, float* scratch, void* stream);
+/* The backward of the trunk's front (conv_bwd_chain_kernel, then the fixed-order sum of its partial dT):
+ * dh2 = gate(Wa[b]^T Xa + Wb^T Xb) with Xa, Xb [B,64,N], Wa [B][64 o][64 i] (sWa floats between instances; 0 = shared),
+ * Wb [64 o][64 i], Zmask the gate bits of the 64 rows; g1 = gate_first(W2t dh2), W2t [64,64]; q = w1^T g1; dx [B,3,N] = T3 q
+ * (T3 [B,9] or NULL = identity); dT [B,9]: dT[d][c] = sum_n x3[d][n] q[c][n].  gate_first = (w1 (T3^T x3) + b1 > 0).
+ * dTpart: B * ceil(N/256) * 32 floats of scratch. */
+int geoa3_debug_conv_bwd_chain(const float* Xa, const float* Wa, int64_t sWa, const float* Xb, const float* Wb,
+                               const void* Zmask, const float* W2t, const float* x3, const float* T3, const float* w1,
+                               const float* b1, float* dx, float* dTpart, float* dT, int B, int N, void* stream);
+/* geoa3_debug_fc with every field of the launch: row pitches, the batch (instance strides sXb / sWb / sYb in floats; batch
+ * 0 / 1 = none), Z [M, ldZ] (keep where Z > 0) and kscratch (ceil(Nout/16) * ceil(M/16) * 4096 floats: K >= 2048 on 16 x 16
+ * tiles is split over four workgroups per tile).  ksplit as geoa3_debug_fc: (tile << 8) | waves. */
+int geoa3_debug_fc_ex(const float* X, int ldX, int64_t sXb, const float* W, int ldW, int64_t sWb, const float* bias,
+                      const float* Z, int ldZ, float* Y, int ldY, int64_t sYb, int M, int Nout, int K, int batch, int relu,
+                      int ksplit, float* kscratch, void* stream);
+
 /* geoa3_grid_nn1_pair (geoa3_hip.h) with its search policy given: brute_frac = the fraction of the searched cloud inside
  * the queries' boxes beyond which a workgroup searches all pairs (0 = always), filter = through the matrix-core filter
  * kernel (1) or the in-kernel sweep (0); negative values = the shipped choice.  Every policy returns the same bits. */
