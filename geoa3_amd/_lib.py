@@ -99,6 +99,13 @@ SIGNATURES = {
     "geoa3_pn2_furthest_point_sampling_ex": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "geoa3_pn2_group_points": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_pn2_group_points_grad": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_pn2_three_nn": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_pn2_three_nn_ex": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "geoa3_pn2_three_nn_tile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "geoa3_pn2_three_interpolate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_pn2_three_interpolate_ex": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "geoa3_pn2_three_interpolate_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "geoa3_pn2_three_interpolate_grad": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_pn2_bias_relu": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, vp]),
     "geoa3_pn2_relu_grad": (C.c_int, [vp, vp, vp, C.c_long, vp]),
     "geoa3_pn2_bias_relu_max": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, C.c_int, vp, vp, vp]),
@@ -164,7 +171,7 @@ _lib = None
 
 ENOSUPPORT = -3   # GEOA3_ENOSUPPORT
 PN2_CONTRACT = 1   # GEOA3_PN2_CONTRACT
-ABI_VERSION = 603  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
+ABI_VERSION = 604  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
 
 
 class Geoa3Error(RuntimeError):

@@ -1,11 +1,10 @@
 """PointNet++ SSG victim (BASELINE configs[3]) on the HIP set-abstraction operators.
 
-Mirrors, for the classifier path only, the three layers of the reference's vendored package
-`Model/pointnet2_ops_lib/pointnet2_ops`:
+Mirrors the three layers of the reference's vendored package `Model/pointnet2_ops_lib/pointnet2_ops`:
   * `ext`  -- the attribute surface of the native module `_ext` (_ext-src/src/bindings.cpp:6-19), each function a
     thin call into libgeoa3_hip.so (geoa3_pn2_*), same argument order, dtypes and fresh-output convention;
-  * the autograd Functions / groupers of pointnet2_utils.py:34-101,194-379;
-  * the set-abstraction modules of pointnet2_modules.py:9-146 and `PointNet2ClassificationSSG`
+  * the autograd Functions / groupers of pointnet2_utils.py:34-379;
+  * the set-abstraction modules of pointnet2_modules.py:9-146, the feature-propagation module (:149-209) and `PointNet2ClassificationSSG`
     (Model/PointNetPP_ssg.py:51-124) with the reference's state_dict keys (SA_modules.{0,1,2}.mlps.0.{0..8}.*,
     fc_layer.{0,1,3,4,7}.*), so `load_state_dict(torch.load(...)['state_dict'])` works (main_attack.py:139-145).
 
@@ -66,8 +65,8 @@ def _ext_flags(contract: Optional[bool]) -> int:
 
 
 class _Ext:
-    """`pointnet2_ops._ext` replacement: same six entry points, backed by the C ABI (`contract`: see
-    ext_contract_default; None = the environment's choice)."""
+    """`pointnet2_ops._ext` replacement: the same nine entry points (bindings.cpp:6-19), backed by the C ABI (`contract`:
+    see ext_contract_default; None = the environment's choice)."""
 
     @staticmethod
     def furthest_point_sampling(xyz: Tensor, nsamples: int, contract: Optional[bool] = None) -> Tensor:
@@ -126,8 +125,52 @@ class _Ext:
                                                       out.data_ptr(), _s()), "group_points_grad")
         return out
 
+    @staticmethod
+    def three_nn(unknown: Tensor, known: Tensor, contract: Optional[bool] = None):
+        """interpolate.cpp:14-40 -> (dist2 [B,n,3] float32, idx [B,n,3] int32); SQUARED distances, as the native function."""
+        _chk(unknown, torch.float32), _chk(known, torch.float32)
+        B, n, _ = unknown.shape
+        m = known.shape[1]
+        dist2 = torch.empty(B, n, 3, device=unknown.device, dtype=torch.float32)
+        idx = torch.empty(B, n, 3, device=unknown.device, dtype=torch.int32)
+        check(_lib.load().geoa3_pn2_three_nn_ex(unknown.data_ptr(), known.data_ptr(), B, n, m, dist2.data_ptr(),
+                                                idx.data_ptr(), _ext_flags(contract), _s()), "three_nn")
+        return dist2, idx
+
+    @staticmethod
+    def three_interpolate(points: Tensor, idx: Tensor, weight: Tensor, contract: Optional[bool] = None) -> Tensor:
+        _chk(points, torch.float32), _chk(idx, torch.int32), _chk(weight, torch.float32)
+        B, C_, m = points.shape
+        n = idx.shape[1]
+        out = torch.empty(B, C_, n, device=points.device, dtype=torch.float32)
+        check(_lib.load().geoa3_pn2_three_interpolate_ex(points.data_ptr(), idx.data_ptr(), weight.data_ptr(), B, C_, m, n,
+                                                         out.data_ptr(), _ext_flags(contract), _s()), "three_interpolate")
+        return out
+
+    @staticmethod
+    def three_interpolate_grad(grad_out: Tensor, idx: Tensor, weight: Tensor, m: int) -> Tensor:
+        _chk(grad_out, torch.float32), _chk(idx, torch.int32), _chk(weight, torch.float32)
+        B, C_, n = grad_out.shape
+        lib = _lib.load()
+        nbytes = lib.geoa3_pn2_three_interpolate_scratch_bytes(B, n, m)
+        if nbytes < 0:
+            raise _lib.Geoa3Error("three_interpolate_grad: sizes out of range (B=%d, n=%d, m=%d)" % (B, n, m))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=grad_out.device)   # the library allocates nothing
+        out = torch.empty(B, C_, m, device=grad_out.device, dtype=torch.float32)
+        check(lib.geoa3_pn2_three_interpolate_grad(grad_out.data_ptr(), idx.data_ptr(), weight.data_ptr(), B, C_, n, m,
+                                                   out.data_ptr(), scratch.data_ptr(), _s()), "three_interpolate_grad")
+        return out
+
 
 ext = _Ext()
+
+
+def three_nn_tiles():
+    """(T, U): the known points per LDS tile and the unknown points per workgroup of the three_nn kernel (for tests that
+    straddle them)."""
+    t, u = C.c_int(0), C.c_int(0)
+    check(_lib.load().geoa3_pn2_three_nn_tile(C.byref(t), C.byref(u)), "three_nn_tile")
+    return t.value, u.value
 
 
 # ------------------------------------------------------------------ pointnet2_utils.py:34-101,194-276
@@ -181,10 +224,43 @@ class _BallQuery(torch.autograd.Function):
         return None, None, None, None
 
 
+class _ThreeNN(torch.autograd.Function):
+    """pointnet2_utils.py:104-136: (dist [B,n,3] = sqrt(dist2), idx [B,n,3]) of the three nearest known points."""
+
+    @staticmethod
+    def forward(ctx, unknown, known):
+        dist2, idx = ext.three_nn(unknown, known)
+        dist = torch.sqrt(dist2)
+        ctx.mark_non_differentiable(dist, idx)
+        return dist, idx
+
+    @staticmethod
+    def backward(ctx, grad_dist, grad_idx):
+        return None, None
+
+
+class _ThreeInterpolate(torch.autograd.Function):
+    """pointnet2_utils.py:139-191: features [B,c,m], idx / weight [B,n,3] -> [B,c,n]; the weights take a zero gradient, as
+    in the reference."""
+
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        ctx.save_for_backward(idx, weight)
+        ctx.m = features.size(2)
+        return ext.three_interpolate(features, idx, weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, weight = ctx.saved_tensors
+        return ext.three_interpolate_grad(g.contiguous(), idx, weight, ctx.m), None, torch.zeros_like(weight)
+
+
 furthest_point_sample = _FPS.apply
 gather_operation = _Gather.apply
 grouping_operation = _Group.apply
 ball_query = _BallQuery.apply
+three_nn = _ThreeNN.apply
+three_interpolate = _ThreeInterpolate.apply
 
 
 class QueryAndGroup(nn.Module):
@@ -277,6 +353,33 @@ class PointnetSAModuleMSG(nn.Module):
 class PointnetSAModule(PointnetSAModuleMSG):
     def __init__(self, mlp, npoint=None, radius=None, nsample=None, bn=True, use_xyz=True):
         super().__init__(mlps=[mlp], npoint=npoint, radii=[radius], nsamples=[nsample], bn=bn, use_xyz=use_xyz)
+
+
+class PointnetFPModule(nn.Module):
+    """pointnet2_modules.py:149-209: propagates the features of the `known` points to the `unknown` ones -- the three nearest
+    known points of each unknown point (three_nn), inverse-distance weights 1 / (dist + 1e-8) normalised over the three,
+    three_interpolate, concatenation with the unknown points' own features, shared MLP.  The search, the interpolation and
+    its feature gradient are the HIP kernels; the MLP (`mlp`, build_shared_mlp: the reference's parameter names, so
+    checkpoints load) stays ordinary torch modules: training mode and weight gradients work through autograd.
+    `known is None`: the reference's branch (:194-197) adds a torch.Size to a list and cannot run on current torch; what it
+    means is implemented -- known_feats [B,C2,1] broadcast to every unknown point, known_feats.expand(B, C2, n)."""
+
+    def __init__(self, mlp: List[int], bn: bool = True):
+        super().__init__()
+        self.mlp = build_shared_mlp(list(mlp), bn=bn)
+
+    def forward(self, unknown: Tensor, known: Optional[Tensor], unknow_feats: Optional[Tensor], known_feats: Tensor) -> Tensor:
+        """unknown [B,n,3], known [B,m,3] or None, unknow_feats [B,C1,n] or None, known_feats [B,C2,m] -> [B,mlp[-1],n]"""
+        if known is not None:
+            dist, idx = three_nn(unknown, known)
+            dist_recip = 1.0 / (dist + 1e-8)
+            norm = torch.sum(dist_recip, dim=2, keepdim=True)
+            weight = dist_recip / norm
+            interpolated = three_interpolate(known_feats, idx, weight)
+        else:
+            interpolated = known_feats.expand(known_feats.size(0), known_feats.size(1), unknown.size(1))
+        new_features = torch.cat([interpolated, unknow_feats], dim=1) if unknow_feats is not None else interpolated
+        return self.mlp(new_features.unsqueeze(-1)).squeeze(-1)
 
 
 def _fold_linear_bn(lin: nn.Linear, bn: Optional[nn.BatchNorm1d]):

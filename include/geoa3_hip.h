@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 603
+#define GEOA3_ABI_VERSION 604
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -317,9 +317,9 @@ int geoa3_attack_begin_search_step(const geoa3_attack_state* st, const float* or
                                    float* offset, float* adam_m, float* adam_v, float* x, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * PointNet++ set-abstraction operators: the functions of the reference's vendored CUDA extension
- * `pointnet2_ops._ext` that the SSG classifier uses (Model/pointnet2_ops_lib/pointnet2_ops/_ext-src/src/
- * bindings.cpp:6-19; three_nn / three_interpolate serve only the segmentation FP module and are out of scope).
+ * PointNet++ operators: the nine functions of the reference's vendored CUDA extension `pointnet2_ops._ext`
+ * (Model/pointnet2_ops_lib/pointnet2_ops/_ext-src/src/bindings.cpp:6-19): the six the SSG classifier uses, and
+ * three_nn / three_interpolate / three_interpolate_grad of the feature-propagation (FP) module.
  * Layouts as in the extension: xyz [B,N,3] point-major, features [B,C,N], indices int32.
  * ------------------------------------------------------------------------------------------ */
 /* sampling.cpp:66-87 / sampling_gpu.cu:69-229.  temp: optional [B,N] scratch that receives the final running
@@ -349,6 +349,32 @@ int geoa3_pn2_group_points(const float* points, const int32_t* idx, int B, int C
 /* group_points.cpp:36-58 / group_points_gpu.cu:43-75: scatter-add into grad_points [B,C,N] (zeroed here) */
 int geoa3_pn2_group_points_grad(const float* grad_out, const int32_t* idx, int B, int C, int N, int M, int nsample,
                                 float* grad_points, void* stream);
+/* interpolate.cpp:14-40 / interpolate_gpu.cu:9-68: for every point of unknown [B,n,3] the three nearest of known [B,m,3],
+ * dist2 [B,n,3] (SQUARED distances, ascending) and idx [B,n,3].  The reference's scan exactly: k = 0 .. m-1 in order, the
+ * strict `<` cascade (equal distances stay in ascending index), NaN / +inf distances never selected, unfilled slots
+ * (m < 3) = (+inf, 0).  Any n, m >= 1.  _ex: `flags` as above (GEOA3_PN2_CONTRACT: the distance of :33 contracted). */
+int geoa3_pn2_three_nn(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx,
+                       void* stream);
+int geoa3_pn2_three_nn_ex(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx,
+                          int flags, void* stream);
+/* the kernel's tile sizes (known points per LDS tile, unknown points per workgroup): for tests that straddle them */
+int geoa3_pn2_three_nn_tile(int* known_tile, int* unknown_tile);
+/* interpolate.cpp:42-70 / interpolate_gpu.cu:72-111: out[b,c,j] = (p[i1] * w1 + p[i2] * w2) + p[i3] * w3 with
+ * p = points[b,c,:] ([B,C,m]), (i1,i2,i3) = idx[b,j,:], (w1,w2,w3) = weight[b,j,:]; out [B,C,n].  Un-fused; _ex with
+ * GEOA3_PN2_CONTRACT: fmaf(p3, w3, fmaf(p2, w2, p1 * w1)).  An index outside [0,m) is the caller's error: it is not
+ * wrapped, the element comes out as NaN. */
+int geoa3_pn2_three_interpolate(const float* points, const int32_t* idx, const float* weight, int B, int C, int m, int n,
+                                float* out, void* stream);
+int geoa3_pn2_three_interpolate_ex(const float* points, const int32_t* idx, const float* weight, int B, int C, int m,
+                                   int n, float* out, int flags, void* stream);
+/* interpolate.cpp:71-99 / interpolate_gpu.cu:116-154: grad_points[b,c,i] = sum over (j,slot) with idx[b,j,slot] == i of
+ * grad_out[b,c,j] * weight[b,j,slot]; grad_points [B,C,m] is written in full (0 where nobody points).  Instead of the
+ * reference's float atomics every destination sums its contributions in ascending (j, slot) order: bit-reproducible,
+ * and row b does not depend on the rest of the batch.  scratch: geoa3_pn2_three_interpolate_scratch_bytes(B, n, m)
+ * bytes (< 0: sizes out of range) for the per-instance counting sort of the 3n entries by destination. */
+int64_t geoa3_pn2_three_interpolate_scratch_bytes(int B, int n, int m);
+int geoa3_pn2_three_interpolate_grad(const float* grad_out, const int32_t* idx, const float* weight, int B, int C, int n,
+                                     int m, float* grad_points, void* scratch, void* stream);
 
 /* Tails of the shared MLPs (pointnet2_modules.py:9-19: Conv2d 1x1 + BatchNorm2d + ReLU; :62-70: max over nsample)
  * around the channel GEMMs, eval mode, BatchNorm scale already folded into the GEMM weights:
