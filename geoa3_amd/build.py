@@ -37,7 +37,7 @@ def _hipcc() -> str:
 # (pointnet_gemm.hip -- the FC heads -- loses 4 % of the iteration without SLP and is left alone.)
 # pointnet2_sa.hip, pointnet2_sa2.hip: relu / max of matrix-core results without the canonicalising v_max x, x the IEEE maxnum semantics put in front
 # of every one of them (a sixth of the level-1 kernels' vector instructions); NaNs still propagate through the products.
-# -fno-slp-vectorize there: the operand split stays at two instructions per element (sa_split2).
+# -fno-slp-vectorize there: the operand split stays at two instructions per element (sf_split2, mfma_split.h).
 # -fno-slp-vectorize: the SLP vectoriser's packed-FP32 instructions (v_pk_add / mul / fma_f32) are behind three sightings of
 # wrong values on gfx950 (NOTEBOOK 5a: conv_bwd_chain_kernel at two waves per SIMD; the sampler beside sa1_fwd_kernel;
 # geo_fused_kernel's long-row path at four waves per SIMD) -- every file compiles without them except the ONE where the

@@ -34,6 +34,13 @@ __device__ __forceinline__ unsigned geoa3_opaque_bits(float x) {
 }
 __device__ __forceinline__ bool geoa3_nonfinite(float x) { return (geoa3_opaque_bits(x) & 0x7fffffffu) >= 0x7f800000u; }
 
+// v_permlane32_swap: a[32..63] <-> b[0..31]
+__device__ __forceinline__ void geoa3_swap32(float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
+
 // wave-wide (64 lanes) reductions with DPP row operations (quad_perm, row_half_mirror, row_mirror, row_bcast15/31):
 // ~10 cycles per step where __shfl_xor compiles to a ds_bpermute round trip through the LDS crossbar.  The result is
 // read from lane 63 and returned uniformly.

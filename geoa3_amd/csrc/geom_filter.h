@@ -19,11 +19,9 @@
 // Clouds whose extent is not finite (or absurd: outside 2^+-60) take the plain exact sweep at the end of search().
 #pragma once
 #include "geom_internal.h"
+#include "mfma_split.h"
 
 namespace nf {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float nf_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int NF_B = 4;                   // blocks of 32 queries per wave: one A operand read feeds four products
 constexpr int NF_QW = 32 * NF_B;          // queries per wave
@@ -45,11 +43,7 @@ __device__ __forceinline__ float nf_abs_or_inf(float a) {   // |a|, +inf for NaN
   const unsigned u = geoa3_opaque_bits(a) & 0x7fffffffu;
   return u >= 0x7f800000u ? NF_INF : __uint_as_float(u);
 }
-__device__ __forceinline__ void nf_split(float u, _Float16& h, _Float16& l) {
-  h = (_Float16)u;
-  l = (_Float16)(u - (float)h);
-}
-__device__ __forceinline__ float nf_min16(const nf_f32x16& a) {   // 8 x v_min3_f32
+__device__ __forceinline__ float nf_min16(const f32x16& a) {   // 8 x v_min3_f32
   const float m0 = fminf(fminf(a[0], a[1]), a[2]), m1 = fminf(fminf(a[3], a[4]), a[5]), m2 = fminf(fminf(a[6], a[7]), a[8]);
   const float m3 = fminf(fminf(a[9], a[10]), a[11]), m4 = fminf(fminf(a[12], a[13]), a[14]);
   return fminf(fminf(fminf(m0, m1), m2), fminf(fminf(m3, m4), a[15]));
@@ -182,9 +176,9 @@ __device__ __forceinline__ void search(const float* __restrict__ P, const float*
     for (int k = 0; k < NF_B; ++k) {
       const float ux = (qx[k] - cx) * us, uy = (qy[k] - cy) * us, uz = (qz[k] - cz) * us;
       _Float16 xh, xl, yh, yl, zh, zl;
-      nf_split(ux, xh, xl);
-      nf_split(uy, yh, yl);
-      nf_split(uz, zh, zl);
+      sf_split(ux, xh, xl);
+      sf_split(uy, yh, yl);
+      sf_split(uz, zh, zl);
       const _Float16 one = (_Float16)1.f, zero = (_Float16)0.f;
       if (kh == 0) {
         Bq[k][0] = xh; Bq[k][1] = xl; Bq[k][2] = xh; Bq[k][3] = yh; Bq[k][4] = yl; Bq[k][5] = yh; Bq[k][6] = zh; Bq[k][7] = zl;
@@ -232,9 +226,9 @@ __device__ __forceinline__ void search(const float* __restrict__ P, const float*
           if (c0 + jl < M) {
             const float ux = (x[u] - cx) * us, uy = (y[u] - cy) * us, uz = (z[u] - cz) * us;
             _Float16 xh, xl, yh, yl, zh, zl;
-            nf_split(ux, xh, xl);
-            nf_split(uy, yh, yl);
-            nf_split(uz, zh, zl);
+            sf_split(ux, xh, xl);
+            sf_split(uy, yh, yl);
+            sf_split(uz, zh, zl);
             const _Float16 m2 = (_Float16)-2.f;
             v0[0] = m2 * xh; v0[1] = m2 * xh; v0[2] = m2 * xl;
             v0[3] = m2 * yh; v0[4] = m2 * yh; v0[5] = m2 * yl;
@@ -242,8 +236,10 @@ __device__ __forceinline__ void search(const float* __restrict__ P, const float*
             const float Pn = ux * ux + uy * uy + uz * uz;
             const _Float16 p0 = (_Float16)Pn;
             const float r1 = Pn - (float)p0;
-            const _Float16 p1 = (_Float16)r1;
-            v1[0] = m2 * zl; v1[1] = p0; v1[2] = p1; v1[3] = (_Float16)(r1 - (float)p1);
+            v1[0] = m2 * zl; v1[1] = p0;
+            _Float16 p1, p2;
+            sf_split(r1, p1, p2);
+            v1[2] = p1; v1[3] = p2;
           } else {
             v1[1] = (_Float16)60000.f;   // rows beyond the cloud: never under a threshold
           }
@@ -299,10 +295,10 @@ __device__ __forceinline__ void search(const float* __restrict__ P, const float*
       half8 a = s_img[lane];
       for (int t = 0; t < (GEOA3_NF_STOP == 1 ? 0 : ntile); ++t) {
         const half8 an = s_img[(t + 1 < ntile ? t + 1 : t) * 64 + lane];      // the next tile's operand while this one multiplies
-        nf_f32x16 acc[NF_B];
+        f32x16 acc[NF_B];
 #pragma unroll
         for (int k = 0; k < NF_B; ++k) {
-          nf_f32x16 z;
+          f32x16 z;
 #pragma unroll
           for (int e = 0; e < 16; ++e) z[e] = 0.f;
           acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, Bq[k], z, 0, 0, 0);

@@ -263,9 +263,9 @@ __device__ __attribute__((noinline)) void grid_filter_sorted(unsigned char* smem
     const float seed_d = __uint_as_float((unsigned)(T0.key[pos[k]] >> 32));
     const float ux = (qx - cx) * us, uy = (qy - cy) * us, uz = (qz - cz) * us;
     _Float16 xh, xl, yh, yl, zh, zl;
-    nf_split(ux, xh, xl);
-    nf_split(uy, yh, yl);
-    nf_split(uz, zh, zl);
+    sf_split(ux, xh, xl);
+    sf_split(uy, yh, yl);
+    sf_split(uz, zh, zl);
     const _Float16 one = (_Float16)1.f, zero = (_Float16)0.f;
     if (kh == 0) {
       Bq[k][0] = xh; Bq[k][1] = xl; Bq[k][2] = xh; Bq[k][3] = yh; Bq[k][4] = yl; Bq[k][5] = yh; Bq[k][6] = zh; Bq[k][7] = zl;
@@ -330,9 +330,9 @@ __device__ __attribute__((noinline)) void grid_filter_sorted(unsigned char* smem
         const float4 r = s_p4[j];
         const float ux = (r.x - cx) * us, uy = (r.y - cy) * us, uz = (r.z - cz) * us;
         _Float16 xh, xl, yh, yl, zh, zl;
-        nf_split(ux, xh, xl);
-        nf_split(uy, yh, yl);
-        nf_split(uz, zh, zl);
+        sf_split(ux, xh, xl);
+        sf_split(uy, yh, yl);
+        sf_split(uz, zh, zl);
         const _Float16 m2 = (_Float16)-2.f;
         v0[0] = m2 * xh; v0[1] = m2 * xh; v0[2] = m2 * xl;
         v0[3] = m2 * yh; v0[4] = m2 * yh; v0[5] = m2 * yl;
@@ -340,8 +340,10 @@ __device__ __attribute__((noinline)) void grid_filter_sorted(unsigned char* smem
         const float Pn = ux * ux + uy * uy + uz * uz;
         const _Float16 p0 = (_Float16)Pn;
         const float r1 = Pn - (float)p0;
-        const _Float16 p1 = (_Float16)r1;
-        v1[0] = m2 * zl; v1[1] = p0; v1[2] = p1; v1[3] = (_Float16)(r1 - (float)p1);
+        v1[0] = m2 * zl; v1[1] = p0;
+        _Float16 p1, p2;
+        sf_split(r1, p1, p2);
+        v1[2] = p1; v1[3] = p2;
       } else {
         v1[1] = (_Float16)60000.f;   // rows beyond the cloud: never under a threshold
       }
@@ -360,10 +362,10 @@ __device__ __attribute__((noinline)) void grid_filter_sorted(unsigned char* smem
 #pragma unroll
       for (int k = 0; k < NF_B; ++k) {
         if (j0 + 31 >= lo[k] && j0 < hi[k]) {     // (wave-uniform)
-          nf_f32x16 z;
+          f32x16 z;
 #pragma unroll
           for (int e = 0; e < 16; ++e) z[e] = 0.f;
-          const nf_f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, Bq[k], z, 0, 0, 0);
+          const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, Bq[k], z, 0, 0, 0);
           const bool hit = nf_min16(acc) <= T[k];
           const unsigned long long mask = __ballot(hit);
           if (mask) {

@@ -259,11 +259,6 @@ constexpr int GPG_CT = 8;
 // at two workgroups per CU), and the 2 x GPG_CT row reductions (totals, padded entries) are done TRANSPOSED: two
 // half-swaps leave every lane with a quarter of the values, four DPP steps finish them -- 40 instructions instead of 16
 // full wave reductions.
-__device__ __forceinline__ void gpg_swap32(float& a, float& b) {   // a[32..63] <-> b[0..31]
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
 __device__ __forceinline__ void gpg_swap16(float& a, float& b) {   // a's odd rows of 16 <-> b's even rows
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   a = __uint_as_float(r[0]);
@@ -324,7 +319,7 @@ __global__ __launch_bounds__(256) void group_points_grad64_kernel(const float* _
         }
 #pragma unroll
         for (int c = 0; c < CT; ++c) {      // lanes 0-31 keep value c, lanes 32-63 value 8 + c
-          gpg_swap32(r[c], r[CT + c]);
+          geoa3_swap32(r[c], r[CT + c]);
           r[c] += r[CT + c];
         }
 #pragma unroll

@@ -36,9 +36,6 @@ constexpr int SA_S = 64;           // samples per centroid
 constexpr int SA_PH = 64 * 2 + 16;    // bytes per row of a 64-k fp16 image (conflict-free 16-byte reads)
 constexpr int SA_PH2 = 128 * 2 + 16;  // bytes per row of the 128-k image (W3^T)
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-
 struct Sa1Lds {
   float* w1;            // backward: [64][3] fp32 rows for the K = 3 contraction
   float* b2;            // [64]
@@ -89,9 +86,10 @@ __device__ __forceinline__ float sa_pow2(int k) {
   return __uint_as_float((unsigned)(k + 127) << 23);
 }
 __device__ __forceinline__ void sa_put(unsigned char* img, int lo_off, int off, float v) {
-  const _Float16 h = (_Float16)v;
+  _Float16 h, l;
+  sf_split(v, h, l);
   *reinterpret_cast<_Float16*>(img + off) = h;
-  *reinterpret_cast<_Float16*>(img + lo_off + off) = (_Float16)(v - (float)h);
+  *reinterpret_cast<_Float16*>(img + lo_off + off) = l;
 }
 __device__ __forceinline__ float sa_relu(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, __builtin_huge_valf()); }
 
@@ -168,9 +166,7 @@ __device__ __forceinline__ void sa1_stage(const geoa3_sa1_weights& w, const Sa1L
     _Float16 hh[4], ll[4];
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-      const float v = (d < 3 ? w.w1[3 * e + d] : w.b1[e]) * s1;
-      hh[d] = (_Float16)v;
-      ll[d] = (_Float16)(v - (float)hh[d]);
+      sf_split((d < 3 ? w.w1[3 * e + d] : w.b1[e]) * s1, hh[d], ll[d]);
     }
     const half8 r0 = {hh[0], hh[1], hh[2], hh[3], hh[0], hh[1], hh[2], ll[3]};
     const half8 r1 = {ll[0], ll[1], ll[2], (_Float16)0.f, ll[0], ll[1], ll[2], (_Float16)0.f};
@@ -207,24 +203,6 @@ __device__ __forceinline__ void sa1_stage(const geoa3_sa1_weights& w, const Sa1L
   __syncthreads();
 }
 
-// (hi, lo) fp16 images of x0 * s and x1 * s, packed: v_pk_mul_f32 + v_cvt_pk_f16_f32 for the pair of hi pieces, one
-// v_fma_mixlo / mixhi_f16 per lo piece (the residual x * s - hi as ONE exact fma, converted and packed by the same
-// instruction): two instructions per element, all of them visible to the compiler's scheduler and hazard recogniser.
-// The file is compiled with -fno-slp-vectorize (geoa3_amd/build.py): the SLP vectoriser turns the pair of residuals into
-// v_cvt_f32_f16 x 2 + v_pk_fma_f32 + v_cvt_pk_f16_f32 (three per element).
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void sa_split2(float x0, float x1, float s, unsigned& hi, unsigned& lo) {
-  const float2v x = {x0, x1};
-  // (the scale as a VECTOR register operand of the packed multiply: packed-FP32 instructions with SGPR-pair operands at
-  // two waves per SIMD are what computed wrong values in conv_bwd_chain_kernel -- NOTEBOOK 5a; none are formed here)
-  float sv = s;
-  asm volatile("" : "+v"(sv));
-  const half2v h = __builtin_convertvector(x * sv, half2v);
-  const half2v l = {(_Float16)__builtin_fmaf(x0, s, -(float)h[0]), (_Float16)__builtin_fmaf(x1, s, -(float)h[1])};
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
 // two accumulator tiles (rows 32 t + mfma_row(r, lane)) -> the operands of the four k-steps that consume them: registers
 // 8 s .. 8 s + 7 of tile t are k-step 2 t + s in the accumulator's row order (the weight images follow it: sa_perm)
 __device__ __forceinline__ void sa_split_tiles(const f32x16 (&v)[2], float s, half8 (&oh)[4], half8 (&ol)[4]) {
@@ -234,7 +212,7 @@ __device__ __forceinline__ void sa_split_tiles(const f32x16 (&v)[2], float s, ha
 #pragma unroll
     for (int j2 = 0; j2 < 4; ++j2) {
       unsigned a, b;
-      sa_split2(v[ks >> 1][8 * (ks & 1) + 2 * j2], v[ks >> 1][8 * (ks & 1) + 2 * j2 + 1], s, a, b);
+      sf_split2(v[ks >> 1][8 * (ks & 1) + 2 * j2], v[ks >> 1][8 * (ks & 1) + 2 * j2 + 1], s, a, b);
       H[j2] = a;
       Lw[j2] = b;
     }
@@ -538,8 +516,9 @@ __global__ __launch_bounds__(SA_T) __attribute__((amdgpu_waves_per_eu(SA_WB / 4,
       kg = sa_k(wave_max(fmaxf(__builtin_fabsf(g0), __builtin_fabsf(g1))));
       const float sg = sa_pow2(kg);
       const float z0 = g0 * sg, z1 = g1 * sg;
-      const _Float16 h0 = (_Float16)z0, h1 = (_Float16)z1;
-      const _Float16 l0 = (_Float16)(z0 - (float)h0), l1 = (_Float16)(z1 - (float)h1);
+      _Float16 h0, l0, h1, l1;
+      sf_split(z0, h0, l0);
+      sf_split(z1, h1, l1);
       s_hp[lane] = (unsigned)__builtin_bit_cast(unsigned short, h0) | (unsigned)__builtin_bit_cast(unsigned short, h1) << 16;
       s_lp[lane] = (unsigned)__builtin_bit_cast(unsigned short, l0) | (unsigned)__builtin_bit_cast(unsigned short, l1) << 16;
       const unsigned a0 = av & 0x3fu, a1 = (av >> 8) & 0x3fu;

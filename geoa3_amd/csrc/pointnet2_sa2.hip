@@ -38,9 +38,9 @@ __global__ __launch_bounds__(256) void frag_image_kernel(const float* __restrict
   m = wave_max(m);
   if (lane == 0) s_m[wave] = m;
   __syncthreads();
-  const unsigned Ew = s2_exp(fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3])));
-  const float sw = s2_scale(Ew);
-  if (tid == 0) un[0] = s2_unscale(Ew);
+  const unsigned Ew = sf_exp(fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3])));
+  const float sw = sf_scale(Ew);
+  if (tid == 0) un[0] = sf_unscale(Ew);
   const int kc = K >> 4;
   for (int e = tid; e < R * K; e += 256) {
     const int row = e / K, k = e - row * K;
@@ -158,19 +158,19 @@ __global__ __launch_bounds__(512) void sa2_fwd8_kernel(Sa2FwdArgs a) {
       mx = wave_max(mx);
       if (lane == 0) s_red[wave] = mx;
       __syncthreads();
-      const unsigned Ea = s2_exp(fmaxf(fmaxf(s_red[4 * ci], s_red[4 * ci + 1]), fmaxf(s_red[4 * ci + 2], s_red[4 * ci + 3])));
-      const float sa = s2_scale(Ea);
+      const unsigned Ea = sf_exp(fmaxf(fmaxf(s_red[4 * ci], s_red[4 * ci + 1]), fmaxf(s_red[4 * ci + 2], s_red[4 * ci + 3])));
+      const float sa = sf_scale(Ea);
 #pragma unroll
       for (int j8 = 0; j8 < 4; ++j8) {
         half8 hh, ll;
         {
           const float x8[8] = {v[8 * j8], v[8 * j8 + 1], v[8 * j8 + 2], v[8 * j8 + 3], v[8 * j8 + 4], v[8 * j8 + 5], v[8 * j8 + 6], v[8 * j8 + 7]};
-          s2_split8(x8, sa, hh, ll);
+          sf_split8(x8, sa, hh, ll);
         }
         *reinterpret_cast<half8*>(thi + lane * S2_PH + (32 * qt + 8 * j8) * 2) = hh;
         *reinterpret_cast<half8*>(tlo + lane * S2_PH + (32 * qt + 8 * j8) * 2) = ll;
       }
-      carry = s2_unscale(Ea);
+      carry = sf_unscale(Ea);
     }
     __syncthreads();
     // ---- B: a1 rows 32 qt .. 32 qt + 31 of centre ci
@@ -236,8 +236,8 @@ __global__ __launch_bounds__(512) void sa2_fwd8_kernel(Sa2FwdArgs a) {
       if (lane == 0) s_red[8 + wave] = mh;
       __syncthreads();   // every wave is done reading a0; the maxima are visible
       const unsigned Eh =
-          s2_exp(fmaxf(fmaxf(s_red[8 + 4 * ci], s_red[9 + 4 * ci]), fmaxf(s_red[10 + 4 * ci], s_red[11 + 4 * ci])));
-      const float sh = s2_scale(Eh);
+          sf_exp(fmaxf(fmaxf(s_red[8 + 4 * ci], s_red[9 + 4 * ci]), fmaxf(s_red[10 + 4 * ci], s_red[11 + 4 * ci])));
+      const float sh = sf_scale(Eh);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -246,8 +246,8 @@ __global__ __launch_bounds__(512) void sa2_fwd8_kernel(Sa2FwdArgs a) {
           half4 hh, ll;
           {
             unsigned h0, l0, h1, l1;
-            s2_split2(acc[cb][4 * g4], acc[cb][4 * g4 + 1], sh, h0, l0);
-            s2_split2(acc[cb][4 * g4 + 2], acc[cb][4 * g4 + 3], sh, h1, l1);
+            sf_split2(acc[cb][4 * g4], acc[cb][4 * g4 + 1], sh, h0, l0);
+            sf_split2(acc[cb][4 * g4 + 2], acc[cb][4 * g4 + 3], sh, h1, l1);
             typedef unsigned uint2v __attribute__((ext_vector_type(2)));
             hh = __builtin_bit_cast(half4, uint2v{h0, h1});
             ll = __builtin_bit_cast(half4, uint2v{l0, l1});
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(512) void sa2_fwd8_kernel(Sa2FwdArgs a) {
           *reinterpret_cast<half4*>(thi + (32 * cb + l31) * S2_PH + k0 * 2) = hh;
           *reinterpret_cast<half4*>(tlo + (32 * cb + l31) * S2_PH + k0 * 2) = ll;
         }
-      carry = s2_unscale(Eh);     // of this wave's centre ci; phase C needs both centres' (below)
+      carry = sf_unscale(Eh);     // of this wave's centre ci; phase C needs both centres' (below)
     }
     __syncthreads();
     // the next pair's gather: in flight across phase C
@@ -304,8 +304,8 @@ __global__ __launch_bounds__(512) void sa2_fwd8_kernel(Sa2FwdArgs a) {
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) {
         const unsigned Eh =
-            s2_exp(fmaxf(fmaxf(s_red[8 + 4 * cc], s_red[9 + 4 * cc]), fmaxf(s_red[10 + 4 * cc], s_red[11 + 4 * cc])));
-        const float un = s2_unscale(Eh) * un2;
+            sf_exp(fmaxf(fmaxf(s_red[8 + 4 * cc], s_red[9 + 4 * cc]), fmaxf(s_red[10 + 4 * cc], s_red[11 + 4 * cc])));
+        const float un = sf_unscale(Eh) * un2;
         float v = -__builtin_inff();
         int smp = 0;
 #pragma unroll
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256) void sa2_pre_kernel(Sa2PreArgs a) {
       x[2] = a.Wx[3 * co + 2];
     }
     half8 wh, wl;
-    s2_split8(x, sw, wh, wl);
+    sf_split8(x, sw, wh, wl);
     s_wx[(t * 2 + 0) * 64 + lane] = wh;
     s_wx[(t * 2 + 1) * 64 + lane] = wl;
   }
@@ -428,13 +428,13 @@ __global__ __launch_bounds__(256) void sa2_pre_kernel(Sa2PreArgs a) {
       q[2] = pz[2];
     }
     mx = fmaxf(mx, fmaxf(__builtin_fabsf(q[0]), fmaxf(__builtin_fabsf(q[1]), __builtin_fabsf(q[2]))));
-    const unsigned Ex = s2_exp(wave_max(mx));
-    const float sx = s2_scale(Ex);
+    const unsigned Ex = sf_exp(wave_max(mx));
+    const float sx = sf_scale(Ex);
     half8 ah[9], al[9];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) s2_split8(raw[c], sx, ah[c], al[c]);
-    s2_split8(q, sx, ah[8], al[8]);
-    const float unscale = s2_unscale(Ex) * unW;
+    for (int c = 0; c < 8; ++c) sf_split8(raw[c], sx, ah[c], al[c]);
+    sf_split8(q, sx, ah[8], al[8]);
+    const float unscale = sf_unscale(Ex) * unW;
     float* Y = a.Y + p0 * S2_K + l31;
 #pragma unroll 1
     for (int t = 0; t < 4; ++t) {

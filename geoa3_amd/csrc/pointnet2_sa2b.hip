@@ -495,9 +495,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();
     // ---- phase 2: rows 64 hf .. 64 hf + 63 of d a0 for the tile's 64 columns
     f32x16 acc2[2][2];
-    const unsigned Ex = s2_exp(fmaxf(s_red[2 * ci], s_red[2 * ci + 1]));
+    const unsigned Ex = sf_exp(fmaxf(s_red[2 * ci], s_red[2 * ci + 1]));
     {
-      const float sx = s2_scale(Ex);
+      const float sx = sf_scale(Ex);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           const float4 b0 = *reinterpret_cast<const float4*>(brow + cb * 32 * S2_PT + c * 16);
           const float4 b1 = *reinterpret_cast<const float4*>(brow + cb * 32 * S2_PT + c * 16 + 4);
           const float x[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-          s2_split8(x, sx, xh[cb], xl[cb]);
+          sf_split8(x, sx, xh[cb], xl[cb]);
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -532,7 +532,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     {
       // gate, un-scale, and the row's coordinate term W_x^T d a0 on the way (this wave's 64 of the 128 i, ascending; W_x rows
       // are uniform: scalar loads); lane = column
-      const float unscale = s2_unscale(Ex) * unW;
+      const float unscale = sf_unscale(Ex) * unW;
       const float* wx = a.Wx + 3 * 64 * hf;
       float y0 = 0.f, y1 = 0.f, y2 = 0.f;
 #pragma unroll
@@ -545,7 +545,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           for (int i = 0; i < 4; ++i) {
             v[i] = acc2[0][t][4 * g + i];
             v[4 + i] = acc2[1][t][4 * g + i];
-            s2_swap32(v[i], v[4 + i]);    // v[i]: row base + i, v[4 + i]: row base + 4 + i, lane = column
+            geoa3_swap32(v[i], v[4 + i]);    // v[i]: row base + i, v[4 + i]: row base + 4 + i, lane = column
           }
 #pragma unroll
           for (int i = 0; i < 8; ++i) {

@@ -13,23 +13,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void cc_swap32(float& a, float& b) {   // a[32..63] <-> b[0..31]
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float cc_first_layer(const float4 w, float p0, float p1, float p2) {
-  return w.x * p0 + w.y * p1 + w.z * p2 + w.w;   // the expression of pointnet_gemm.hip first_layer (same bits)
-}
-__device__ __forceinline__ unsigned cc_exp(float m) {   // as cs_exp (pointnet_conv_split.hip)
-  const unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
-  return E < 14u ? 14u : (E > 254u ? 254u : E);
-}
-__device__ __forceinline__ float cc_scale(unsigned E) { return __uint_as_float((267u - E) << 23); }
-__device__ __forceinline__ float cc_unscale(unsigned E) { return __uint_as_float((E - 13u) << 23); }
-
 // d[lane l] = v (wave-uniform value, constant lane): one instruction instead of compare + select
 __device__ __forceinline__ void cc_writelane(int& d, int v, int l) {
   asm("v_writelane_b32 %0, %1, %2" : "+v"(d) : "s"(v), "n"(l));
@@ -56,7 +39,7 @@ __device__ __forceinline__ void cc_mm(const float (&xin)[64], const unsigned cha
     float m = 0.f;
 #pragma unroll
     for (int u = 0; u < 16; ++u) m = fmaxf(m, __builtin_fabsf(x[u]));
-    const unsigned E = cc_exp(wave_max(live ? m : 0.f));   // = the maximum over the live lanes' |x| (0 for the others)
+    const unsigned E = sf_exp(wave_max(live ? m : 0.f));   // = the maximum over the live lanes' |x| (0 for the others)
     if (E > Ex) {   // wave-uniform: shrink the scale, rescale the sums (exact)
       if (c > 0) {
         const unsigned d = E - Ex;
@@ -70,12 +53,12 @@ __device__ __forceinline__ void cc_mm(const float (&xin)[64], const unsigned cha
       }
       Ex = E;
     }
-    const float sx = cc_scale(Ex);
+    const float sx = sf_scale(Ex);
     half8 xh[2], xl[2];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float v0 = x[j] * sx, v1 = x[8 + j] * sx;
-      cc_swap32(v0, v1);    // v0: column block 0, v1: column block 1; lanes (column, k half)
+      geoa3_swap32(v0, v1);    // v0: column block 0, v1: column block 1; lanes (column, k half)
       const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
       xh[0][j] = h0;
       xl[0][j] = (_Float16)(v0 - (float)h0);
@@ -105,7 +88,7 @@ __device__ __forceinline__ void cc_rows(const f32x16 (&acc)[2][2], float (&out)[
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float v0 = acc[0][t][4 * g + i], v1 = acc[1][t][4 * g + i];
-        cc_swap32(v0, v1);    // v0: row base + i, v1: row base + 4 + i
+        geoa3_swap32(v0, v1);    // v0: row base + i, v1: row base + 4 + i
         out[t * 32 + 8 * g + i] = v0;
         out[t * 32 + 8 * g + 4 + i] = v1;
       }
@@ -127,8 +110,8 @@ __device__ __forceinline__ void cc_wload(const float* W, bool kcontig, int tid, 
 // ... scaled by the block's power of two and split into the two fp16 images [64][CC_PITCH] at s_wh; returns the exponent
 __device__ __forceinline__ unsigned cc_wsplit(const float (&wv)[16], bool kcontig, int tid, const float* s_red,
                                               unsigned char* s_wh) {
-  const unsigned Ew = cc_exp(fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
-  const float sw = cc_scale(Ew);
+  const unsigned Ew = sf_exp(fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
+  const float sw = sf_scale(Ew);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int e = tid + 256 * i;
@@ -194,7 +177,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       p2 = x0 * t[2] + x1 * t[5] + x2 * t[8];
     }
 #pragma unroll
-    for (int u = 0; u < 64; ++u) o[u] = fmaxf(cc_first_layer(s_w1[u], p0, p1, p2), 0.f);
+    for (int u = 0; u < 64; ++u) o[u] = fmaxf(pn_first_layer(s_w1[u], p0, p1, p2), 0.f);
   } else {   // all 64 rows in flight at once
     const float* X = a.X + (size_t)b * a.sXb;      // uniform row base + lane offset: scalar-base addressing
     const unsigned xc = (unsigned)(live ? col : a.N - 1);
@@ -212,7 +195,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     f32x16 acc[2][2];   // [column block][row tile]
     unsigned Ex;
     cc_mm(o, arow, live, acc, Ex);
-    const float unscale = cc_unscale(Ex) * cc_unscale(Ew[blk]);
+    const float unscale = sf_unscale(Ex) * sf_unscale(Ew[blk]);
 
     // epilogue: every pair of accumulator registers becomes two 64-column rows (row, row + 4); bias + relu; the row's
     // gate bits go to the stage's mask word (lane = row), the row itself into o[] -- the next stage's input, and what is
@@ -311,7 +294,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // W3eff^T Ga
   cc_mm(o, arow, live, acc, Ex);
   {
-    const float un = cc_unscale(Ex) * cc_unscale(Ew[0]);
+    const float un = sf_unscale(Ex) * sf_unscale(Ew[0]);
     cc_rows(acc, o);
 #pragma unroll
     for (int r = 0; r < 64; ++r) o[r] *= un;
@@ -319,7 +302,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // + Wc1^T Gb, then the relu gate of h2
   cc_mm(xb, arow + CC_BLK, live, acc, Ex);
   {
-    const float un = cc_unscale(Ex) * cc_unscale(Ew[1]);
+    const float un = sf_unscale(Ex) * sf_unscale(Ew[1]);
     cc_rows(acc, res);
     const unsigned sh = lane & 31;
 #pragma unroll
@@ -335,14 +318,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   cc_mm(o, arow + 2 * CC_BLK, live, acc, Ex);
   float q0 = 0.f, q1 = 0.f, q2 = 0.f;
   {
-    const float un = cc_unscale(Ex) * cc_unscale(Ew[2]);
+    const float un = sf_unscale(Ex) * sf_unscale(Ew[2]);
     cc_rows(acc, res);
     if (live) {
 #pragma unroll
       for (int r = 0; r < 64; ++r) {
         float v = res[r] * un;
         const float4 w = s_w1[r];
-        v = cc_first_layer(w, p0, p1, p2) > 0.f ? v : 0.f;
+        v = pn_first_layer(w, p0, p1, p2) > 0.f ? v : 0.f;
         q0 = fmaf(w.x, v, q0);
         q1 = fmaf(w.y, v, q1);
         q2 = fmaf(w.z, v, q2);

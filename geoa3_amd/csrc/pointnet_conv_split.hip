@@ -9,7 +9,7 @@
 // access one 256-byte row, K in chunks of 16 rows double-buffered in registers.  Differences:
 //   * the 64 x K weight block is scaled by a power of two from its own maximum, split, and kept in LDS as two fp16
 //     images [64][K] (rows padded by 16 B: the A operand of a k-step is one conflict-free ds_read_b128);
-//   * a chunk of 16 rows is one k-step: v_permlane32_swap of rows (j, 8 + j) yields, for both 32-column blocks, the
+//   * a chunk of 16 rows is one k-step: geoa3_swap32 of rows (j, 8 + j) yields, for both 32-column blocks, the
 //     B-operand element j of lanes (column, k half) -- the same swap that builds the fp32 operands;
 //   * the activation scale is a RUNNING per-wave power of two: when a later chunk's maximum exceeds the range of the
 //     current scale, the accumulators are rescaled (exact) and the scale shrinks; a chunk of smaller values keeps
@@ -18,24 +18,6 @@
 #include "pointnet_kernels.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void cs_swap32(float& a, float& b) {   // a[32..63] <-> b[0..31]
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float cs_first_layer(const float4 w, float p0, float p1, float p2) {
-  return w.x * p0 + w.y * p1 + w.z * p2 + w.w;   // the expression of pointnet_gemm.hip first_layer (same bits)
-}
-// biased exponent E of m clamped to [14, 254]; scale 2^(140 - E) puts m into [2^13, 2^14); unscale 2^(E - 140)
-__device__ __forceinline__ unsigned cs_exp(float m) {
-  const unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
-  return E < 14u ? 14u : (E > 254u ? 254u : E);
-}
-__device__ __forceinline__ float cs_scale(unsigned E) { return __uint_as_float((267u - E) << 23); }
-__device__ __forceinline__ float cs_unscale(unsigned E) { return __uint_as_float((E - 13u) << 23); }
 
 template <int NCH, bool FIRST, bool GFIRST, bool BWD3, int PN2 = 0, bool IMG = false, bool DEEP = false>  // K = 16 * NCH; BWD3 needs GFIRST;
                                                                   // PN2: 1 = pooled output, 2 = one-hot input,
@@ -176,9 +158,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
       if (lane == 0) s_red[wave] = m;
     }
     __syncthreads();
-    Ew = cs_exp(fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
+    Ew = sf_exp(fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
     {
-      const float sw = cs_scale(Ew);
+      const float sw = sf_scale(Ew);
   #pragma unroll
       for (int i = 0; i < WPT; ++i) {
         const int e = tid + 256 * i;
@@ -217,7 +199,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
     const int c = c0 + cc;
     if (FIRST) {
 #pragma unroll
-      for (int u = 0; u < CH; ++u) xb[cc % NB][u] = fmaxf(cs_first_layer(s_w1[CH * c + u], p0, p1, p2), 0.f);
+      for (int u = 0; u < CH; ++u) xb[cc % NB][u] = fmaxf(pn_first_layer(s_w1[CH * c + u], p0, p1, p2), 0.f);
     } else if (c + NB - 1 < NCH) {
       load_rows(c + NB - 1, xb[(cc + NB - 1) % NB]);
     }
@@ -225,7 +207,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
     float m = 0.f;
 #pragma unroll
     for (int u = 0; u < CH; ++u) m = fmaxf(m, __builtin_fabsf(live ? x[u] : 0.f));
-    const unsigned E = cs_exp(wave_max(m));
+    const unsigned E = sf_exp(wave_max(m));
     if (E > Ex) {   // wave-uniform: larger values than any chunk before -- shrink the scale, rescale the sums (exact)
       if (c > 0) {
         const unsigned d = E - Ex;
@@ -239,12 +221,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
       }
       Ex = E;
     }
-    const float sx = cs_scale(Ex);
+    const float sx = sf_scale(Ex);
     half8 xh[2], xl[2];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float v0 = x[j] * sx, v1 = x[8 + j] * sx;
-      cs_swap32(v0, v1);    // v0: column block 0, v1: column block 1; lanes (column, k half)
+      geoa3_swap32(v0, v1);    // v0: column block 0, v1: column block 1; lanes (column, k half)
       const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
       xh[0][j] = h0;
       xl[0][j] = (_Float16)(v0 - (float)h0);
@@ -271,7 +253,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
       }
     }
   }
-  const float unscale = cs_unscale(Ex) * (IMG ? a.Wun[0] : cs_unscale(Ew));
+  const float unscale = sf_unscale(Ex) * (IMG ? a.Wun[0] : sf_unscale(Ew));
 
   if (PN2 == 3) {
     // pack2 layout, N = 128: waves 2 i, 2 i + 1 hold columns 0-63 / 64-127 of instance 2 z + i.  Per wave as PN2 == 1
@@ -357,7 +339,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
       for (int i = 0; i < 4; ++i) {
         v[i] = acc[0][t][4 * g + i];
         v[4 + i] = acc[1][t][4 * g + i];
-        cs_swap32(v[i], v[4 + i]);    // v[i]: row base+i, v[4+i]: row base+4+i, lane = column
+        geoa3_swap32(v[i], v[4 + i]);    // v[i]: row base+i, v[4+i]: row base+4+i, lane = column
       }
       const int row0 = rb * 64 + t * 32 + 8 * g;   // rows row0 .. row0+7 in the order of v[]
       if (a.Zmask && wave_live) {
@@ -385,7 +367,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
           if (a.relu) o = fmaxf(o, 0.f);
           if (a.accumulate) o += y[i];
           if (Z || a.Zmask) o = z[i] > 0.f ? o : 0.f;  // gate AFTER accumulation (sum of branches, then relu')
-          if (GFIRST) o = cs_first_layer(s_w1[row0 + i], p0, p1, p2) > 0.f ? o : 0.f;
+          if (GFIRST) o = pn_first_layer(s_w1[row0 + i], p0, p1, p2) > 0.f ? o : 0.f;
           if (BWD3) {
             const float4 w = s_w1[row0 + i];
             q0 = fmaf(w.x, o, q0);

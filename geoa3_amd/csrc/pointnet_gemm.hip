@@ -13,25 +13,15 @@ namespace {
 // 256-byte row (lane = column): measured on MI355X, a store instruction covering ONE 256-B row runs at 5.7 TB/s
 // while the same bytes as two 128-B segments in two rows (a 32x32 accumulator register as it stands) reach only
 // 2.2 TB/s (tools/bench_conv.py), which made the 32-column form of this kernel store-bound.  The MFMA operand
-// layouts (two rows x 32 columns per register) are produced in registers by v_permlane32_swap: swapping the upper
+// layouts (two rows x 32 columns per register) are produced in registers by geoa3_swap32: swapping the upper
 // half of row 2s with the lower half of row 2s+1 turns two 64-column rows into the B operands of the two 32-column
 // blocks, and the same swap on a pair of accumulator registers turns them into two 64-column output rows.
 // K is consumed in chunks of 32 rows, double-buffered in registers: chunk c+1 is in flight while chunk c feeds the
 // matrix core; chunk 0 is requested before the weights are staged into LDS.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void swap32(float& a, float& b) {   // a[32..63] <-> b[0..31]
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-
 // FIRST: the input rows are the 3-channel first layer, computed on the fly (ConvArgs::produce_first);
 // GFIRST: the output's relu gate is that first layer's sign, recomputed (ConvArgs::gate_first).  Both evaluate
-// relu(w1 . (T^T x) + b1) with ONE expression (first_layer), so the forward activation and the backward mask agree.
-__device__ __forceinline__ float first_layer(const float4 w, float p0, float p1, float p2) {
-  return w.x * p0 + w.y * p1 + w.z * p2 + w.w;
-}
-
+// relu(w1 . (T^T x) + b1) with ONE expression (pn_first_layer), so the forward activation and the backward mask agree.
 template <int NCH, bool FIRST, bool GFIRST, bool BWD3>  // K = CH * NCH; BWD3 needs GFIRST
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) void conv_cm64_kernel(ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s_w[];  // [64][K+1]: the 64 output rows of this row block
@@ -112,7 +102,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
   for (int c = 0; c < NCH; ++c) {
     if (FIRST) {
 #pragma unroll
-      for (int u = 0; u < CH; ++u) xb[c & 1][u] = fmaxf(first_layer(s_w1[CH * c + u], p0, p1, p2), 0.f);
+      for (int u = 0; u < CH; ++u) xb[c & 1][u] = fmaxf(pn_first_layer(s_w1[CH * c + u], p0, p1, p2), 0.f);
     } else if (c + 1 < NCH) {
 #pragma unroll
       for (int u = 0; u < CH; ++u) xb[(c + 1) & 1][u] = X[(size_t)(CH * (c + 1) + u) * a.ldX];
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
     float* x = xb[c & 1];
 #pragma unroll
     for (int u = 0; u < CH / 2; ++u) {
-      swap32(x[2 * u], x[2 * u + 1]);
+      geoa3_swap32(x[2 * u], x[2 * u + 1]);
       const float a0 = wrow[CH * c + 2 * u], a1 = wrow[32 * pitch + CH * c + 2 * u];
       acc[0][0] = mfma32(a0, x[2 * u], acc[0][0]);
       acc[1][0] = mfma32(a0, x[2 * u + 1], acc[1][0]);
@@ -145,7 +135,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
       for (int i = 0; i < 4; ++i) {
         v[i] = acc[0][t][4 * g + i];
         v[4 + i] = acc[1][t][4 * g + i];
-        swap32(v[i], v[4 + i]);    // v[i]: row base+i, v[4+i]: row base+4+i, lane = column
+        geoa3_swap32(v[i], v[4 + i]);    // v[i]: row base+i, v[4+i]: row base+4+i, lane = column
       }
       const int row0 = rb * 64 + t * 32 + 8 * g;   // rows row0 .. row0+7 in the order of v[]
       if (a.Zmask && wave_live) {                  // wave-uniform 8-byte loads: bit `lane` gates this lane's column
@@ -173,7 +163,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
           if (a.relu) o = fmaxf(o, 0.f);
           if (a.accumulate) o += y[i];
           if (Z || a.Zmask) o = z[i] > 0.f ? o : 0.f;  // gate AFTER accumulation (sum of branches, then relu')
-          if (GFIRST) o = first_layer(s_w1[row0 + i], p0, p1, p2) > 0.f ? o : 0.f;
+          if (GFIRST) o = pn_first_layer(s_w1[row0 + i], p0, p1, p2) > 0.f ? o : 0.f;
           if (BWD3) {
             const float4 w = s_w1[row0 + i];
             q0 += w.x * o;
@@ -262,8 +252,6 @@ __global__ __launch_bounds__(256) void reduce_dT_kernel(const float* __restrict_
 //   * the S partial tiles meet in LDS and are summed in wave order (fixed order: results do not depend on timing or on
 //     the batch size), each wave finishing one accumulator register (a row group) incl. bias / relu / gate and its store.
 // ------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void load4(const float* p, int k, int kend, bool vec, float v[4]) {
   if (vec && k + 3 < kend) {
     const float4 t = *reinterpret_cast<const float4*>(p + k);

@@ -13,19 +13,12 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 constexpr int GR_CHK = 128;                  // columns per chunk (one power-of-two scale per matrix and chunk)
 constexpr int GR_HALF = GR_CHK / 2;          // columns in LDS at a time: a chunk goes through the images in two halves --
                                              // 35 KB per workgroup instead of 70, four workgroups per CU instead of two
                                              // (the kernel is bound by HBM latency: 51 -> 30.5 us at B = 250, N = 1024)
 constexpr int GR_PITCH = GR_HALF * 2 + 16;   // bytes per LDS row (conflict-free 16-byte reads: 36 banks = 4 mod 32)
 constexpr int GR_IMG = 64 * GR_PITCH;        // one piece of one matrix
-
-__device__ __forceinline__ unsigned gr_exp(float m) {
-  const unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
-  return E < 14u ? 14u : (E > 254u ? 254u : E);
-}
 
 __global__ __launch_bounds__(256) void gram64_kernel(const float* __restrict__ A, const float* __restrict__ G, int N,
                                                      float* __restrict__ P, int parts) {
@@ -71,9 +64,9 @@ __global__ __launch_bounds__(256) void gram64_kernel(const float* __restrict__ A
       s_red[1][wave] = mg;
     }
     __syncthreads();
-    const unsigned Ea = gr_exp(fmaxf(fmaxf(s_red[0][0], s_red[0][1]), fmaxf(s_red[0][2], s_red[0][3])));
-    const unsigned Eg = gr_exp(fmaxf(fmaxf(s_red[1][0], s_red[1][1]), fmaxf(s_red[1][2], s_red[1][3])));
-    const float sa = __uint_as_float((267u - Ea) << 23), sg = __uint_as_float((267u - Eg) << 23);
+    const unsigned Ea = sf_exp(fmaxf(fmaxf(s_red[0][0], s_red[0][1]), fmaxf(s_red[0][2], s_red[0][3])));
+    const unsigned Eg = sf_exp(fmaxf(fmaxf(s_red[1][0], s_red[1][1]), fmaxf(s_red[1][2], s_red[1][3])));
+    const float sa = sf_scale(Ea), sg = sf_scale(Eg);
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -103,7 +96,7 @@ __global__ __launch_bounds__(256) void gram64_kernel(const float* __restrict__ A
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, gh, acc, 0, 0, 0);
       }
     }
-    const float un = __uint_as_float((Ea - 13u) << 23) * __uint_as_float((Eg - 13u) << 23);
+    const float un = sf_unscale(Ea) * sf_unscale(Eg);
 #pragma unroll
     for (int i = 0; i < 16; ++i) sum[i] += acc[i] * un;
   }

@@ -1,10 +1,8 @@
 // Internal launch interface between pointnet.hip (orchestration) and the kernel translation units.
 #pragma once
-#include "common.h"
+#include "mfma_split.h"
 
 constexpr int GEOA3_DT_PITCH = 32;   // floats per row of the dT3 partial sums (ConvArgs::dTpart)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // exact-fp32 matrix core op: D(32x32) += A(32x2) * B(2x32).  Lane l supplies A[l&31][l>>5] and
 // B[l>>5][l&31]; D[i][j]: j = l&31, i = (reg&3) + 8*(reg>>2) + 4*(l>>5).
@@ -57,6 +55,11 @@ struct ConvArgs {
   const void* Wimg; const float* Wun; int img_kc, img_c0;
 };
 int launch_conv_cm(const ConvArgs& a, hipStream_t s);         // dispatches on a.split
+// The folded first layer before its relu, w = (w1 row, b1), p = T^T x: the ONE expression of every kernel that produces the
+// activation (produce_first) or recomputes its gate (gate_first), so forward activation and backward mask agree in every bit.
+__device__ __forceinline__ float pn_first_layer(const float4 w, float p0, float p1, float p2) {
+  return w.x * p0 + w.y * p1 + w.z * p2 + w.w;
+}
 
 // A chain of 64-input layers with relu in one kernel (pointnet_conv_chain.hip; split arithmetic, the bits of the
 // layer-by-layer launches): stage i reads the 64 rows stage i - 1 produced (stage 0: X [B][64][N], or, with x3, the folded

@@ -24,9 +24,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int W16_THREADS = 256;
 constexpr int W16_OCC = 2;                        // workgroups per CU
 constexpr int W16_PTS = 128;
@@ -34,11 +31,6 @@ constexpr int W16_ROWS = W16_PTS + 2;
 constexpr int W16_ROWB = 288;
 constexpr int W16_PIECEB = W16_ROWS * W16_ROWB;   // 37,440
 constexpr int W16_LDS = 2 * W16_PIECEB;           // 74,880 B: two workgroups per CU
-
-__device__ __forceinline__ void w16_split(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)(v - (float)hi);
-}
 
 __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a, int slots_per_xcd) {
   constexpr int TAPS = 3;
@@ -115,8 +107,8 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
     m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
     unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
     bool bad = E == 255u;
-    E = E < 14u ? 14u : (E > 254u ? 254u : E);
-    const float scale = __uint_as_float((267u - E) << 23), unscale = a.unscale * __uint_as_float((E - 13u) << 23);
+    E = sf_clamp(E);
+    const float scale = sf_scale(E), unscale = a.unscale * sf_unscale(E);
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
       const int p = 1 + pass * 64 + lane;
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
           const float xs = xv[pass][oc][i] * scale;
           bad |= xs != xs;
           _Float16 h, l;
-          w16_split(xs, h, l);
+          sf_split(xs, h, l);
           hi[i] = h;
           lo[i] = l;
         }
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
       const float xs = xhalo * scale;
       bad |= xs != xs;
       _Float16 h, l;
-      w16_split(xs, h, l);
+      sf_split(xs, h, l);
       unsigned char* dst = smem_raw + (tid < 128 ? 0 : W16_ROWS - 1) * W16_ROWB + (tid & 127) * 2;
       *reinterpret_cast<_Float16*>(dst) = h;
       *reinterpret_cast<_Float16*>(dst + W16_PIECEB) = l;

@@ -21,15 +21,7 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 constexpr int WM_CI = 128;
-
-__device__ __forceinline__ unsigned bc_exp(float m) {
-  const unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
-  return E < 14u ? 14u : (E > 254u ? 254u : E);
-}
-__device__ __forceinline__ float bc_scale(unsigned E) { return __uint_as_float((267u - E) << 23); }
-__device__ __forceinline__ float bc_unscale(unsigned E) { return __uint_as_float((E - 13u) << 23); }
 
 constexpr int BW2_WAVES = 8, BW2_THREADS = 64 * BW2_WAVES;
 #ifdef GEOA3_BC_STAMPS   // probe build: s_memtime at the phase boundaries of a few workgroups (tools/bc_stamps.py)
@@ -325,11 +317,10 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
   float tm = s_mx[0];
 #pragma unroll
   for (int w = 1; w < BW2_WAVES; ++w) tm = fmaxf(tm, s_mx[w]);
-  const unsigned Ex = bc_exp(tm);
-  const float sx = bc_scale(Ex);
+  const unsigned Ex = sf_exp(tm);
+  const float sx = sf_scale(Ex);
   constexpr int BC_PH = 2 * BC_PT;   // halves per column of the images
   _Float16* s_img = reinterpret_cast<_Float16*>(s_acc);
-  typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float x0 = tv[2 * j] * sx, x1 = tv[2 * j + 1] * sx;
@@ -368,7 +359,7 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
     }
   }
   BC_STAMP(7);
-  const float un = bc_unscale(Ex) * a.w2th_unscale;
+  const float un = sf_unscale(Ex) * a.w2th_unscale;
   // acc[r]: row 32 qt + (r&3) + 8 (r>>2) + 4 (lane>>5), column 32 qc + (lane&31); gate word of row l in lane l of gw2
   const int col = 32 * qc + (lane & 31), m = m0 + col;
   if constexpr (GF) {

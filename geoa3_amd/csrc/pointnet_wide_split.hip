@@ -31,19 +31,12 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 constexpr int SP_THREADS = 256;
 constexpr int SP_OCC = 2;                    // workgroups per CU
 constexpr int SP_PTS = 128;                  // points per unit
 constexpr int SP_ROWB = 272;                 // bytes per LDS row: 128 fp16 + 16 B pad (row stride = 4 banks mod 64)
 constexpr int SP_PIECEB = SP_PTS * SP_ROWB;  // 34,816
 constexpr int SP_LDS = 2 * SP_PIECEB;        // 69,632 B: two workgroups per CU
-
-__device__ __forceinline__ void split16(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)(v - (float)hi);
-}
 
 __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs a, int slots_per_xcd) {
   constexpr int GROUPS = 8;                  // channel groups of 128 per unit
@@ -135,11 +128,10 @@ __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs
     if (lane == 0) s_max[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    // scale = 2^e with max * 2^e in [2^13, 2^14)
     unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
     bool bad = E == 255u;    // inf (a NaN does not survive fmaxf: caught below)
-    E = E < 14u ? 14u : (E > 254u ? 254u : E);
-    const float scale = __uint_as_float((267u - E) << 23), unscale = a.unscale * __uint_as_float((E - 13u) << 23);
+    E = sf_clamp(E);
+    const float scale = sf_scale(E), unscale = a.unscale * sf_unscale(E);
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
       const int p = pass * 64 + lane;
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs
           const float xs = xv[pass][oc][i] * scale;
           bad |= xs != xs;
           _Float16 h, l;
-          split16(xs, h, l);
+          sf_split(xs, h, l);
           hi[i] = h;
           lo[i] = l;
         }
