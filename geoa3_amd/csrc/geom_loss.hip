@@ -1411,14 +1411,18 @@ extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
   if ((a->w_curv != 0.f || a->dkappa) && (!a->knn_adv || !a->normal_ori || !a->i_ao || a->k <= 0))
     return GEOA3_EINVAL;
   if (a->w_curv != 0.f && !a->dkappa && !a->kappa_ori) return GEOA3_EINVAL;
+  // what the choice of kernel rests on, derived once (the kernels' do_curv / two_side / Nr)
+  const int N = a->N, Nr = a->Nr > 0 ? a->Nr : a->N;
   const bool do_curv = (a->w_curv != 0.f || a->dkappa) && a->knn_adv;
+  const bool two_side = a->dis_type == 1 && !a->single_side && a->d_oa != nullptr;
+  const bool ordered = a->deterministic || !a->grad;   // a reproducible gradient, or none at all
+  hipStream_t s = geoa3_stream(stream);
+
+  // ---- 1. the pair-parallel kernel, if the instance fits: the cloud, its normals, coefficients and own terms (10 N floats),
+  // row lengths, and one row of C source ids per point; rows of 2 (k + clean points per point) + 16 ids (in-degrees of a
+  // k-NN graph concentrate around k), at least 32, at most what fits
   // (k > 32 with a scratch buffer: the fixed-point kernel below -- geo_fused_kernel<64> carries 272 bytes of scratch per lane)
-  if ((a->deterministic || !a->grad) && a->N <= GEO_T && a->k <= 64 && !(a->k > 32 && a->scratch && do_curv)) {
-    // the pair-parallel kernel: the cloud, its normals, coefficients and own terms (10 N floats), row lengths, and one row
-    // of C source ids per point; rows of 2 (k + clean points per point) + 16 ids (in-degrees of a k-NN graph concentrate
-    // around k), at least 32, at most what fits
-    const int N = a->N, Nr = a->Nr > 0 ? a->Nr : a->N;
-    const bool two_side = a->dis_type == 1 && !a->single_side && a->d_oa != nullptr;
+  if (ordered && N <= GEO_T && a->k <= 64 && !(a->k > 32 && a->scratch && do_curv)) {
     if (two_side && !a->i_oa) return GEOA3_EINVAL;
     const int per = (do_curv ? a->k : 0) + (two_side ? (Nr + N - 1) / N : 0);
     const size_t fixed = ((size_t)12 * N + 16 * 5 + 4) * sizeof(float);
@@ -1435,7 +1439,6 @@ extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
       const size_t lds = fixed + (size_t)R * (C + 1) * sizeof(uint16_t) + GEO_POOL_BYTES;
       int G = 1;
       while (G < a->k && do_curv) G *= 2;
-      hipStream_t s = geoa3_stream(stream);
       geoa3_prof_begin(GEOA3_PROF_GEO, s);
 #define GEOA3_FUSED_CASE(GG)                                                                                           \
   if (G == GG) {                                                                                                       \
@@ -1456,46 +1459,41 @@ extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
       return GEOA3_OK;
     }
   }
-  if ((a->deterministic || !a->grad) && a->scratch && do_curv && (a->N > GEO_T || a->k > 32) && a->N <= 4096 && a->k <= 64) {
-    // the pair-parallel kernel with fixed-point sums (see geo_big_kernel)
-    const int N = a->N;
-    const bool two_side = a->dis_type == 1 && !a->single_side && a->d_oa != nullptr;
+  // ---- 2. else the pair-parallel kernel with fixed-point sums (see geo_big_kernel), given the caller's scratch buffer
+  if (ordered && a->scratch && do_curv && (N > GEO_T || a->k > 32) && N <= 4096 && a->k <= 64) {
     if (two_side && !a->i_oa) return GEOA3_EINVAL;
-    {
-      int G = 1;
-      while (G < a->k) G *= 2;
-      if (G < 16) G = 16;
-      float4* ctr = reinterpret_cast<float4*>(a->scratch);
-      hipStream_t s = geoa3_stream(stream);
-      const size_t lds2 = (size_t)36 * N + (16 * 5 + 4) * sizeof(float) + 8 + GB_POOL_CAP * (3 * 8 + 4) + ((size_t)(N + 31) / 32) * 4;
-      geoa3_prof_begin(GEOA3_PROF_GEO, s);
-      hipLaunchKernelGGL(geo_big_gather_kernel, dim3((N + 255) / 256, a->B), dim3(256), 0, s, *a, ctr);
+    int G = 1;
+    while (G < a->k) G *= 2;
+    if (G < 16) G = 16;
+    float4* ctr = reinterpret_cast<float4*>(a->scratch);
+    const size_t lds2 = (size_t)36 * N + (16 * 5 + 4) * sizeof(float) + 8 + GB_POOL_CAP * (3 * 8 + 4) + ((size_t)(N + 31) / 32) * 4;
+    geoa3_prof_begin(GEOA3_PROF_GEO, s);
+    hipLaunchKernelGGL(geo_big_gather_kernel, dim3((N + 255) / 256, a->B), dim3(256), 0, s, *a, ctr);
 #define GEOA3_BIG_CASE(GG)                                                                                             \
   if (G == GG) {                                                                                                       \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_big_kernel<GG>),                                       \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                  \
     hipLaunchKernelGGL(geo_big_kernel<GG>, dim3(a->B), dim3(GB_T), lds2, s, *a, ctr);                                  \
   }
-      GEOA3_BIG_CASE(16)
-      GEOA3_BIG_CASE(32)
-      GEOA3_BIG_CASE(64)
+    GEOA3_BIG_CASE(16)
+    GEOA3_BIG_CASE(32)
+    GEOA3_BIG_CASE(64)
 #undef GEOA3_BIG_CASE
-      geoa3_prof_end(GEOA3_PROF_GEO, s);
-      GEOA3_CHECK_LAUNCH();
-      return GEOA3_OK;
-    }
+    geoa3_prof_end(GEOA3_PROF_GEO, s);
+    GEOA3_CHECK_LAUNCH();
+    return GEOA3_OK;
   }
-  const size_t base = ((size_t)7 * a->N + GEO_WAVES * 5 + 4) * sizeof(float);
+  // ---- 3. else the one-workgroup kernel: owner lists where they fit beside the cloud, LDS float atomics otherwise
+  const size_t base = ((size_t)7 * N + GEO_WAVES * 5 + 4) * sizeof(float);
   if (base > 160 * 1024) return GEOA3_ENOSUPPORT;  // N <= ~5800 points per instance
-  const size_t det_idx = ((size_t)a->N + 1) * sizeof(int);
+  const size_t idx = ((size_t)N + 1) * sizeof(int);
   // (clouds whose reverse lists do not fit beside the cloud -- N > ~4800 -- take the atomic kernel: same values, free
   // summation order, documented in geoa3_hip.h)
-  if (a->deterministic && a->grad && base + det_idx + 2048 * sizeof(int) <= 160 * 1024 - 512) {
+  if (a->deterministic && a->grad && base + idx + 2048 * sizeof(int) <= 160 * 1024 - 512) {
     // counts / offsets, then (if they fit) the per-point normals, then the reverse lists of one chunk of sources: all of
     // them in one chunk when they fit (N = 1024, k = 16: 70 KB), at least 2048 entries otherwise
-    const size_t Nr = a->Nr > 0 ? a->Nr : a->N;
-    const size_t idx = ((size_t)a->N + 1) * sizeof(int), nrm = (size_t)3 * a->N * sizeof(float);
-    const size_t cap = 160 * 1024 - 512, all = (size_t)a->N * a->k > Nr ? (size_t)a->N * a->k : Nr;
+    const size_t nrm = (size_t)3 * N * sizeof(float);
+    const size_t cap = 160 * 1024 - 512, all = (size_t)N * a->k > (size_t)Nr ? (size_t)N * a->k : (size_t)Nr;
     const int nrm_in = a->normal_ori && base + idx + nrm + (all < 8192 ? all : 8192) * sizeof(int) <= cap;
     size_t rcap = (cap - base - idx - (nrm_in ? nrm : 0)) / sizeof(int);
     if (rcap > all) rcap = all;
@@ -1503,10 +1501,9 @@ extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
     const size_t lds = base + idx + (nrm_in ? nrm : 0) + rcap * sizeof(int);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_loss_grad_kernel<true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    geoa3_prof_begin(GEOA3_PROF_GEO, geoa3_stream(stream));
-    hipLaunchKernelGGL(geo_loss_grad_kernel<true>, dim3(a->B), dim3(GEO_BLOCK), lds, geoa3_stream(stream), *a, (int)rcap,
-                       nrm_in);
-    geoa3_prof_end(GEOA3_PROF_GEO, geoa3_stream(stream));
+    geoa3_prof_begin(GEOA3_PROF_GEO, s);
+    hipLaunchKernelGGL(geo_loss_grad_kernel<true>, dim3(a->B), dim3(GEO_BLOCK), lds, s, *a, (int)rcap, nrm_in);
+    geoa3_prof_end(GEOA3_PROF_GEO, s);
     GEOA3_CHECK_LAUNCH();
     return GEOA3_OK;
   }
@@ -1514,9 +1511,9 @@ extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_loss_grad_kernel<false>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  geoa3_prof_begin(GEOA3_PROF_GEO, geoa3_stream(stream));
-  hipLaunchKernelGGL(geo_loss_grad_kernel<false>, dim3(a->B), dim3(GEO_BLOCK), lds, geoa3_stream(stream), *a, 0, 0);
-  geoa3_prof_end(GEOA3_PROF_GEO, geoa3_stream(stream));
+  geoa3_prof_begin(GEOA3_PROF_GEO, s);
+  hipLaunchKernelGGL(geo_loss_grad_kernel<false>, dim3(a->B), dim3(GEO_BLOCK), lds, s, *a, 0, 0);
+  geoa3_prof_end(GEOA3_PROF_GEO, s);
   GEOA3_CHECK_LAUNCH();
   return GEOA3_OK;
 }
