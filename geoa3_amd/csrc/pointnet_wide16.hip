@@ -1,8 +1,8 @@
 // conv5 (the trunk's 1024-wide layer: kernel 3, pad 1) on the 16x16x32 shape of the f16 matrix core (gfx950).
 //
 // Same arithmetic as pointnet_wide_split.hip (every fp32 operand as hi + lo fp16 values, a*w = a_hi*w_hi + a_hi*w_lo +
-// a_lo*w_hi, fp32 accumulate, per-unit power-of-two activation scale), same work units, same keys / finalize; what
-// changes is the MFMA shape: `v_mfma_f32_16x16x32_f16` takes the same cycles per flop as `32x32x16`, but the chip holds a
+// a_lo*w_hi, fp32 accumulate, per-unit power-of-two activation scale), same keys / finalize; what changes is the MFMA
+// shape: `v_mfma_f32_16x16x32_f16` takes the same cycles per flop as `32x32x16`, but the chip holds a
 // higher clock on it under 16-bit matrix load (MI355X_MICROARCH.md, DVFS give-back item 7: 1.12-1.15x the FLOP/s at
 // equal cycles).  Measured on MI355X: conv5 (K = 384 per channel group) 0.495 ms on the 32x32x16 kernel, 0.444 ms here;
 // the T-Nets' conv3 (K = 128: a third of the MFMAs between two epilogues) goes the other way (0.182 ms there, 0.292 ms
@@ -19,6 +19,14 @@
 //     two-step register ring that runs across the channel groups.
 // The A fragments are double-buffered by HALF k-steps (four point tiles): the half just consumed is refilled for the next
 // k-step while the other half's 24 MFMAs run.
+//
+// A work unit is (instance, 128-point tile, all 8 groups of 128 channels), as in the T-Net kernel: a tile is read, scaled,
+// split and written to LDS once.  (Until the unit was widened a tile's two channel halves were separate units and each
+// staged the tile for itself: conv5 alone at B = 250, N = 1024 449.0 -> 428.9 us, same bits; NOTEBOOK 10, "conv5
+// dissected".)  The two workgroups of a CU still run half a unit (now four groups) apart.  The unit's 4 x 8 x 32 packed
+// maxima wait for their atomicMax in the padding bytes of the image's rows: a second 8 KB array beside the 74,880-byte
+// image would leave no room for two workgroups per CU.  The kernel sits at 256 registers and spills (19 VGPRs, 80 bytes
+// per lane), but every scratch access lies in the staging part of the unit loop, none inside the channel-group or k loops.
 #include "pointnet_kernels.h"
 #include "profile.h"
 
@@ -32,19 +40,32 @@ constexpr int W16_ROWB = 288;
 constexpr int W16_PIECEB = W16_ROWS * W16_ROWB;   // 37,440
 constexpr int W16_LDS = 2 * W16_PIECEB;           // 74,880 B: two workgroups per CU
 
+// Timing-only variant builds (tools/gpu_w16_dissect.sh, never the shipped library): a bit mask of phases compiled out.
+//   1 = no staging (the LDS image is left as it is), 2 = no epilogue / keys, 4 = no weight-fragment loads (ring reused)
+#ifndef GEOA3_W16_CUT
+#define GEOA3_W16_CUT 0
+#endif
+
 __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a, int slots_per_xcd) {
   constexpr int TAPS = 3;
-  constexpr int GROUPS = 4;                  // channel groups of 128 per unit
+  constexpr int GROUPS = 8;                  // channel groups of 128 per unit: all 1024 channels, one staging pass per tile
   constexpr int KS = TAPS * 4;               // k-steps of 32 per channel tile
   constexpr int PF = 2;                      // k-steps of weight fragments in flight
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ float s_max[4];
-  __shared__ unsigned long long s_keys[4][GROUPS][32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p16 = lane & 15, q4 = lane >> 4, l31 = lane & 31,
             kh = lane >> 5;
+  // packed maxima of the current unit, published while the next unit is staged (pointnet_wide_split.hip).  They live in
+  // the 32 pad bytes of the image's rows (4 keys per row, 2 x 128 rows = the 4 x 8 x 32 keys of a unit): neither the
+  // staging writes nor the A reads touch bytes 256..287 of a row, and a second 8 KB array would not leave room for two
+  // workgroups per CU
+  auto key_slot = [&](int i, int l) {   // channel tile i (< GROUPS) of this wave, channel l (< 32)
+    const int k = (wave * GROUPS + i) * 32 + l;
+    unsigned char* row = smem_raw + (k >> 9) * W16_PIECEB + ((k >> 2) & 127) * W16_ROWB;
+    return reinterpret_cast<unsigned long long*>(row + 256 + (k & 3) * 8);
+  };
   const int N = a.N, tiles = (N + W16_PTS - 1) / W16_PTS;
-  constexpr int SPLIT = 8 / GROUPS;
-  const int per_inst = tiles * SPLIT;
+  const int per_inst = tiles;
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int inst_x = (a.B - xcd + 7) / 8;
   const int units = inst_x * per_inst;
@@ -59,7 +80,7 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
   auto flush = [&]() {
     if (pend_b < 0) return;
     for (int i = kh; i < pend_n; i += 2)
-      atomicMax(a.keys + (size_t)pend_b * a.Co + pend_co + i * 128 + l31, s_keys[wave][i][l31]);
+      atomicMax(a.keys + (size_t)pend_b * a.Co + pend_co + i * 128 + l31, *key_slot(i, l31));
     pend_b = -1;
   };
   for (int it = 0; it < nmine + (late ? 1 : 0); ++it) {
@@ -67,79 +88,86 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
     const int g_begin = late && it == nmine ? GROUPS / 2 : 0;
     const int g_end = late && it == 0 ? GROUPS / 2 : GROUPS;
     const int qi = u / per_inst, r = u - qi * per_inst;
-    const int b = xcd + 8 * qi, tile = r / SPLIT, half = r - tile * SPLIT;
+    const int b = xcd + 8 * qi, tile = r;
     const int n0 = tile * W16_PTS;
     const float* X = a.X + (size_t)b * a.sXb;
     // ---- stage (as in the 32x32 kernel): maximum -> scale -> split -> LDS, rows 1..128 = points n0 .. n0 + 127;
     // the two halo rows (points n0 - 1, n0 + 128): one value per thread
-    float xv[2][4][8], xhalo = 0.f;
-    {
-      int ldx = a.ldX;
-      asm volatile("" : "+s"(ldx));
+    float unscale = a.unscale;
+    if (GEOA3_W16_CUT & 1) {
+      flush();
+      __syncthreads();
+    } else {
+      float xv[2][4][8], xhalo = 0.f;
+      {
+        int ldx = a.ldX;
+        asm volatile("" : "+s"(ldx));
 #pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int n = n0 + pass * 64 + lane;
-        const bool in = n < N;
-        const float* px = X + (in ? n : 0);
+        for (int pass = 0; pass < 2; ++pass) {
+          const int n = n0 + pass * 64 + lane;
+          const bool in = n < N;
+          const float* px = X + (in ? n : 0);
+#pragma unroll
+          for (int oc = 0; oc < 4; ++oc)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              const float v = px[(size_t)(((wave + 4 * oc) * 8 + i) * ldx)];
+              xv[pass][oc][i] = in ? v : 0.f;
+            }
+        }
+        const int nh = tid < 128 ? n0 - 1 : n0 + W16_PTS;
+        if (nh >= 0 && nh < N) xhalo = X[(size_t)((tid & 127) * ldx) + nh];
+      }
+      float m = __builtin_fabsf(xhalo);
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass)
 #pragma unroll
         for (int oc = 0; oc < 4; ++oc)
 #pragma unroll
+          for (int i = 0; i < 8; ++i) m = fmaxf(m, __builtin_fabsf(xv[pass][oc][i]));
+      m = wave_max(m);
+      flush();
+      __syncthreads();
+      if (lane == 0) s_max[wave] = m;
+      __syncthreads();
+      m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+      unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
+      bool bad = E == 255u;
+      E = sf_clamp(E);
+      const float scale = sf_scale(E);
+      unscale = a.unscale * sf_unscale(E);
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass) {
+        const int p = 1 + pass * 64 + lane;
+#pragma unroll
+        for (int oc = 0; oc < 4; ++oc) {
+          half8 hi, lo;
+#pragma unroll
           for (int i = 0; i < 8; ++i) {
-            const float v = px[(size_t)(((wave + 4 * oc) * 8 + i) * ldx)];
-            xv[pass][oc][i] = in ? v : 0.f;
+            const float xs = xv[pass][oc][i] * scale;
+            bad |= xs != xs;
+            _Float16 h, l;
+            sf_split(xs, h, l);
+            hi[i] = h;
+            lo[i] = l;
           }
-      }
-      const int nh = tid < 128 ? n0 - 1 : n0 + W16_PTS;
-      if (nh >= 0 && nh < N) xhalo = X[(size_t)((tid & 127) * ldx) + nh];
-    }
-    float m = __builtin_fabsf(xhalo);
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass)
-#pragma unroll
-      for (int oc = 0; oc < 4; ++oc)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) m = fmaxf(m, __builtin_fabsf(xv[pass][oc][i]));
-    m = wave_max(m);
-    flush();
-    __syncthreads();
-    if (lane == 0) s_max[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
-    bool bad = E == 255u;
-    E = sf_clamp(E);
-    const float scale = sf_scale(E), unscale = a.unscale * sf_unscale(E);
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      const int p = 1 + pass * 64 + lane;
-#pragma unroll
-      for (int oc = 0; oc < 4; ++oc) {
-        half8 hi, lo;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float xs = xv[pass][oc][i] * scale;
-          bad |= xs != xs;
-          _Float16 h, l;
-          sf_split(xs, h, l);
-          hi[i] = h;
-          lo[i] = l;
+          unsigned char* dst = smem_raw + p * W16_ROWB + (wave + 4 * oc) * 16;
+          *reinterpret_cast<half8*>(dst) = hi;
+          *reinterpret_cast<half8*>(dst + W16_PIECEB) = lo;
         }
-        unsigned char* dst = smem_raw + p * W16_ROWB + (wave + 4 * oc) * 16;
-        *reinterpret_cast<half8*>(dst) = hi;
-        *reinterpret_cast<half8*>(dst + W16_PIECEB) = lo;
       }
+      {
+        const float xs = xhalo * scale;
+        bad |= xs != xs;
+        _Float16 h, l;
+        sf_split(xs, h, l);
+        unsigned char* dst = smem_raw + (tid < 128 ? 0 : W16_ROWS - 1) * W16_ROWB + (tid & 127) * 2;
+        *reinterpret_cast<_Float16*>(dst) = h;
+        *reinterpret_cast<_Float16*>(dst + W16_PIECEB) = l;
+      }
+      if (__syncthreads_or(bad))
+        for (int c = tid; c < a.Co; c += W16_THREADS) atomicMax(a.keys + (size_t)b * a.Co + c, ~0ull);
     }
-    {
-      const float xs = xhalo * scale;
-      bad |= xs != xs;
-      _Float16 h, l;
-      sf_split(xs, h, l);
-      unsigned char* dst = smem_raw + (tid < 128 ? 0 : W16_ROWS - 1) * W16_ROWB + (tid & 127) * 2;
-      *reinterpret_cast<_Float16*>(dst) = h;
-      *reinterpret_cast<_Float16*>(dst + W16_PIECEB) = l;
-    }
-    if (__syncthreads_or(bad))
-      for (int c = tid; c < a.Co; c += W16_THREADS) atomicMax(a.keys + (size_t)b * a.Co + c, ~0ull);
     // A operand of lane (p16, q4), point tile t, k-step s (tap = s / 4, ci0 = 32 (s % 4)):
     //   row 16 t + p16 + tap, bytes (ci0 + 8 q4) * 2
     const unsigned char* abase = smem_raw + p16 * W16_ROWB + q4 * 16;
@@ -150,7 +178,7 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
     };
     // weight fragments of the wave's channel tile c2 (< 2) of group g: [T16][s][piece][lane]
     auto wbase = [&](int g, int c2) {
-      const int co = (half * GROUPS + g) * 128 + wave * 32 + 16 * c2;
+      const int co = g * 128 + wave * 32 + 16 * c2;
       return Wall + (size_t)(co / 16) * KS * 2 * 64 + lane;
     };
     half8 wf[PF][2][2];
@@ -196,6 +224,7 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
           for (int c2 = 0; c2 < 2; ++c2) {
             wh[c2] = wf[f][c2][0];
             wl[c2] = wf[f][c2][1];
+            if (GEOA3_W16_CUT & 4) continue;
             const half8* src = s + PF < KS ? Wp[c2] + (size_t)(2 * 64) * (s + PF) : Wn[c2] + (size_t)(2 * 64) * (s + PF - KS);
             wf[f][c2][0] = src[0];
             wf[f][c2][1] = src[64];
@@ -220,6 +249,13 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
       }
       // lane: channel co0 + 16 c2 + p16; acc[t][c2][r]: point n0 + 16 t + 4 q4 + r.  Ascending point order, strict >
       const bool full = n0 + W16_PTS <= N;
+      if (GEOA3_W16_CUT & 2) {   // the accumulators stay live, nothing is reduced or published
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+#pragma unroll
+          for (int c2 = 0; c2 < 2; ++c2) asm volatile("" ::"v"(acc[t][c2]));
+        continue;
+      }
 #pragma unroll
       for (int c2 = 0; c2 < 2; ++c2) {
         float v = -__builtin_inff();
@@ -241,11 +277,12 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
           v = take ? ov : v;
           col = take ? oc : col;
         }
-        if (lane < 16) s_keys[wave][g - g_begin][16 * c2 + lane] = wide_key(v * unscale, col);
+        if (lane < 16) *key_slot(g - g_begin, 16 * c2 + lane) = wide_key(v * unscale, col);
       }
     }
+    if (GEOA3_W16_CUT & 2) continue;
     pend_b = b;
-    pend_co = (half * GROUPS + g_begin) * 128 + wave * 32;
+    pend_co = g_begin * 128 + wave * 32;
     pend_n = g_end - g_begin;
   }
   flush();
