@@ -25,10 +25,17 @@
 // staged the tile for itself: conv5 alone at B = 250, N = 1024 449.0 -> 428.9 us, same bits; NOTEBOOK 10, "conv5
 // dissected".)  The two workgroups of a CU still run half a unit (now four groups) apart.  The unit's 4 x 8 x 32 packed
 // maxima wait for their atomicMax in the padding bytes of the image's rows: a second 8 KB array beside the 74,880-byte
-// image would leave no room for two workgroups per CU.  The kernel sits at 256 registers and spills (19 VGPRs, 80 bytes
+// image would leave no room for two workgroups per CU.  The kernel sits at 256 registers and spills (14 VGPRs, 60 bytes
 // per lane), but every scratch access lies in the staging part of the unit loop, none inside the channel-group or k loops.
+//
+// Epilogue of a channel group (wide_epilogue.h): the lane's maximum first (v_max3_f32), then the lowest point whose
+// accumulator equals it (one compare + one select per value, no branch), then the shuffles across the four lanes of a
+// channel.  Points past the end of a ragged tile are set to -inf beforehand.  (The one-pass `(full || n < N) && x > v`
+// scan it replaces had compiled to an exec-mask region with a branch per value: conv5 alone 442.3 -> 419.8 us, same bits;
+// NOTEBOOK 10.  Running the next group's first k-step under the index scan was built as well and lost: NOTEBOOK 8 row 41.)
 #include "pointnet_kernels.h"
 #include "profile.h"
+#include "wide_epilogue.h"
 
 namespace {
 
@@ -256,24 +263,27 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
           for (int c2 = 0; c2 < 2; ++c2) asm volatile("" ::"v"(acc[t][c2]));
         continue;
       }
-#pragma unroll
-      for (int c2 = 0; c2 < 2; ++c2) {
-        float v = -__builtin_inff();
-        int col = 0;
+      if (!full) {               // points past the end lose to every valid one (point n0 is valid and finite)
+        const int left = N - n0 - 4 * q4;
 #pragma unroll
         for (int t = 0; t < 8; ++t)
 #pragma unroll
-          for (int r4 = 0; r4 < 4; ++r4) {
-            const int n = n0 + 16 * t + 4 * q4 + r4;
-            const bool gt = (full || n < N) && acc[t][c2][r4] > v;
-            v = gt ? acc[t][c2][r4] : v;
-            col = gt ? n : col;
-          }
+          for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) acc[t][c2][r4] = 16 * t + r4 < left ? acc[t][c2][r4] : -__builtin_inff();
+      }
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2) {
+        float v;
+        int col;
+        wide_lane_first_max<32>([&](int i) { return acc[i >> 2][c2][i & 3]; }, [](int i) { return 16 * (i >> 2) + (i & 3); },
+                                v, col);
+        col += n0 + 4 * q4;
 #pragma unroll
         for (int o = 16; o <= 32; o <<= 1) {
           const float ov = __shfl_xor(v, o, 64);
           const int oc = __shfl_xor(col, o, 64);
-          const bool take = ov > v || (ov == v && oc < col);
+          const bool take = wide_merge_take(ov, oc, v, col);
           v = take ? ov : v;
           col = take ? oc : col;
         }

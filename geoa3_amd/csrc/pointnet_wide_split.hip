@@ -24,10 +24,13 @@
 // activation tile is split while it is staged and stored POINT-major in LDS ([piece][point][128 ci] fp16, rows padded to
 // 272 B), so the A operand of a k-step (8 consecutive ci of one point) is one conflict-free ds_read_b128; each wave owns
 // CB x 32 channels x 128 points (4 point tiles per channel tile); the weight fragments stream from L2 (2 x 16 B per lane per
-// channel tile and k-step of 16) through a register ring across the channel groups.  Epilogue, keys and the finalize
-// kernel are those of the fp32 path.
+// channel tile and k-step of 16) through a register ring across the channel groups.  Keys and the finalize kernel are
+// those of the fp32 path; the epilogue is the two-pass, branch-free first maximum of wide_epilogue.h (the lane's maximum
+// over its 64 values, then the lowest point that equals it; ragged tiles masked to -inf first): the layer alone 188.0 ->
+// 183.4 us against the one-pass compare / select chain, same bits (NOTEBOOK 10).
 #include "pointnet_kernels.h"
 #include "profile.h"
+#include "wide_epilogue.h"
 
 namespace {
 
@@ -37,6 +40,12 @@ constexpr int SP_PTS = 128;                  // points per unit
 constexpr int SP_ROWB = 272;                 // bytes per LDS row: 128 fp16 + 16 B pad (row stride = 4 banks mod 64)
 constexpr int SP_PIECEB = SP_PTS * SP_ROWB;  // 34,816
 constexpr int SP_LDS = 2 * SP_PIECEB;        // 69,632 B: two workgroups per CU
+
+// Timing-only variant builds (tools/build_w16_variants.sh, never the shipped library), the bit of pointnet_wide16.hip's
+// GEOA3_W16_CUT: 2 = no epilogue / keys
+#ifndef GEOA3_WSP_CUT
+#define GEOA3_WSP_CUT 0
+#endif
 
 __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs a, int slots_per_xcd) {
   constexpr int GROUPS = 8;                  // channel groups of 128 per unit
@@ -236,40 +245,40 @@ __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs
       stamp();
       // lane: channel co0 + l31; acc[t][r]: point n0 + 32t + (r&3) + 8(r>>2) + 4kh.  Ascending point order, strict >
       const bool full = n0 + SP_PTS <= N;
+      if (GEOA3_WSP_CUT & 2) {   // the accumulators stay live, nothing is reduced or published
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) asm volatile("" ::"v"(acc[c][t]));
+        continue;
+      }
+      if (!full) {               // points past the end lose to every valid one (point n0 is valid and finite)
+        const int left = N - n0 - 4 * kh;
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r16 = 0; r16 < 16; ++r16)
+              acc[c][t][r16] = 32 * t + mfma_row(r16, 0) < left ? acc[c][t][r16] : -__builtin_inff();
+      }
 #pragma unroll
       for (int c = 0; c < CB; ++c) {
-        float v = -__builtin_inff();
-        int col = 0;
-        if (full) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r16 = 0; r16 < 16; ++r16) {
-              const bool gt = acc[c][t][r16] > v;
-              v = gt ? acc[c][t][r16] : v;
-              col = gt ? 32 * t + mfma_row(r16, 0) : col;
-            }
-          col += n0 + 4 * kh;
-        } else {
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r16 = 0; r16 < 16; ++r16) {
-              const int n = n0 + 32 * t + mfma_row(r16, lane);
-              const bool gt = n < N && acc[c][t][r16] > v;
-              v = gt ? acc[c][t][r16] : v;
-              col = gt ? n : col;
-            }
-        }
+        float v;
+        int col;
+        wide_lane_first_max<64>([&](int i) { return acc[c][i >> 4][i & 15]; },
+                                [](int i) { return 32 * (i >> 4) + mfma_row(i & 15, 0); }, v, col);
+        col += n0 + 4 * kh;
         const float ov = __shfl_xor(v, 32, 64);
         const int oc = __shfl_xor(col, 32, 64);
-        const bool take = ov > v || (ov == v && oc < col);
+        const bool take = wide_merge_take(ov, oc, v, col);
         v = take ? ov : v;
         col = take ? oc : col;
         if (lane < 32) s_keys[wave][(g - g_begin) * CB + c][lane] = wide_key(v * unscale, col);
       }
     }
     stamp();
+    if (GEOA3_WSP_CUT & 2) continue;
     pend_b = b;
     pend_co = (half * GROUPS + g_begin * CB) * 128 + wave * 32 * CB;
     pend_n = (g_end - g_begin) * CB;
