@@ -169,7 +169,6 @@ class AttackRunner:
         if self.use_curv:
             t["knn"] = [torch.zeros(b, ne, self.k + 1, **i32) for _ in range(2)]
             t["knn_d"] = z(b, ne, self.k + 1)
-            self.knn_slab = True
             self.knn_method = int(_cfg(cfg, "knn_method", 0))   # geoa3_knn_self: 0 = by (K, N), 1 = slab, 2 = cell grid
             t["knn_scratch"] = ops.knn_self_scratch(b, ne, device)
         if self.w_knn != 0:
@@ -404,7 +403,7 @@ class AttackRunner:
                 prior, out = t["knn"][self.knn_cur], t["knn"][1 - self.knn_cur]
                 check(lib.geoa3_knn_self(xe.data_ptr(), self.b, ne, self.k + 1,
                                          prior.data_ptr() if self.knn_seeded else None, t["knn_d"].data_ptr(),
-                                         out.data_ptr(), t["knn_scratch"].data_ptr() if self.knn_slab else None,
+                                         out.data_ptr(), t["knn_scratch"].data_ptr(),
                                          self.knn_method, sg),
                       "knn_self")
                 self.knn_seeded = True

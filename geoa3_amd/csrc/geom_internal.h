@@ -1,4 +1,5 @@
-// Internal launchers of the exact searches, shared between geom_nn.hip (all pairs), geom_grid.hip and geom_slab.hip.
+// Internal launchers of the exact searches, shared between geom_nn.hip (all pairs), geom_grid.hip and geom_filter.hip (1-NN),
+// geom_slab.hip (self K-NN: slab search and routing) and geom_knn_grid.hip (self K-NN: cell grid).
 #pragma once
 #include "common.h"
 // `only`: optional per-query byte flags ([ndir][B][max(Na,Nr)] for nn1, [B][Nq] for knn): search ONLY those queries
@@ -7,6 +8,11 @@ int geoa3_launch_nn1(const float* a, const float* r, int B, int Na, int Nr, floa
                      int32_t* i_ra, const uint8_t* only, hipStream_t s);
 int geoa3_launch_knn(const float* q, const float* r, int B, int Nq, int Nr, int K, const int32_t* prior, float* dists,
                      int32_t* idx, const uint8_t* only, hipStream_t s);
+// The cell-grid self K-NN (geom_knn_grid.hip; chosen by geoa3_knn_self, geom_slab.hip): N <= 8192, K <= min(N, GEOA3_KNN_MAX_K),
+// prior [B,N,K] given, scratch 256-byte aligned and of geoa3_knn_cellgrid_scratch_bytes(B, N) bytes.
+size_t geoa3_knn_cellgrid_scratch_bytes(int B, int N);
+int geoa3_launch_knn_cellgrid(const float* pc, int B, int N, int K, const int32_t* prior, float* dists, int32_t* idx,
+                              void* scratch, hipStream_t s);
 // Grid-accelerated exact K=1 search (geom_grid.hip); GEOA3_ENOSUPPORT when a cloud exceeds 4096 points.
 int geoa3_launch_grid_nn1(const float* a, const float* r, int B, int Na, int Nr, const int32_t* prior_ar,
                           const int32_t* prior_ra, float* d_ar, int32_t* i_ar, float* d_ra, int32_t* i_ra, hipStream_t s);

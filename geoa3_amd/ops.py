@@ -87,8 +87,11 @@ def knn_self_scratch(B: int, N: int, device) -> Tensor:
 
 def knn_self_planar(pc: Tensor, K: int, prior: Optional[Tensor] = None, scratch: Optional[Tensor] = None,
                     out=None, method: int = 0) -> Tuple[Tensor, Tensor]:
-    """== knn_planar(pc, pc, K, prior) bit for bit; pruned when prior and scratch are given (method 1: slab along the
-    longest axis, 2: cell grid with one wavefront per query, 0: by (K, N))."""
+    """== knn_planar(pc, pc, K, prior) bit for bit; pruned when prior and scratch (knn_self_scratch) are given, N <= 8192
+    and K <= N.  method (GEOA3_KNN_SELF_* of geoa3_hip.h) 0: the cell grid for K > 20 or N >= 2048, else the slab search;
+    1: slab along the longest axis (position lists for launches of more than 512 workgroups, else (distance, index) lists);
+    2: cell grid with one wavefront per query; 3 / 4: slab with (distance, index) / position lists whatever the launch size.
+    _lib.load().geoa3_debug_knn_self_route names the kernel a call takes."""
     B, _, N = pc.shape
     if out is None:
         d = torch.empty(B, N, K, device=pc.device, dtype=torch.float32)

@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 604
+#define GEOA3_ABI_VERSION 605
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -88,6 +88,11 @@ int geoa3_knn(const float* q, const float* r, int B, int Nq, int Nr, int K,
  * Without `prior` or `scratch`, or for N > 8192, it runs the all-pairs kernel.  scratch:
  * geoa3_knn_self_scratch_bytes(B, N) bytes, 256-byte aligned, contents irrelevant.
  * Replaces knn_points(adv, adv, K=k+1) at Lib/loss_utils.py:77. */
+#define GEOA3_KNN_SELF_AUTO 0            /* `method`; any other value behaves as GEOA3_KNN_SELF_SLAB */
+#define GEOA3_KNN_SELF_SLAB 1
+#define GEOA3_KNN_SELF_GRID 2
+#define GEOA3_KNN_SELF_SLAB_LISTS 3
+#define GEOA3_KNN_SELF_SLAB_POSITIONS 4
 int64_t geoa3_knn_self_scratch_bytes(int B, int N);
 int geoa3_knn_self(const float* pc, int B, int N, int K, const int32_t* prior, float* dists, int32_t* idx,
                    void* scratch, int method, void* stream);

@@ -96,6 +96,19 @@ int geoa3_debug_grid_nn1_pair(const float* a, const float* r, int B, int Na, int
                               const int32_t* prior_ra, float* d_ar, int32_t* i_ar, float* d_ra, int32_t* i_ra,
                               float brute_frac, int filter, void* stream);
 
+/* The search geoa3_knn_self (geoa3_hip.h) would run for these sizes, `method`, with / without a prior and a usable (non-NULL,
+ * 256-byte aligned) scratch buffer: one of GEOA3_KNN_ROUTE_*, or GEOA3_EINVAL where geoa3_knn_self refuses the sizes.  No
+ * GPU work.  Every route returns the same bits, so this is the one place the choice can be observed
+ * (tests/test_knn_self_route.py). */
+#define GEOA3_KNN_ROUTE_ALLPAIRS 0   /* geoa3_knn's kernel: nothing to prune with, N > 8192 or K > N */
+#define GEOA3_KNN_ROUTE_CELLGRID 1   /* knn_cellsort_kernel + knn_grid_kernel */
+#define GEOA3_KNN_ROUTE_SLAB40 2     /* slab_bin_kernel + knn_slab_kernel<40 / 72 / 96>: (distance, index) lists */
+#define GEOA3_KNN_ROUTE_SLAB72 3
+#define GEOA3_KNN_ROUTE_SLAB96 4
+#define GEOA3_KNN_ROUTE_SLABP32 5    /* slab_bin_kernel + knn_slabp_kernel<32, false> / <56, true>: position lists */
+#define GEOA3_KNN_ROUTE_SLABP56 6
+int geoa3_debug_knn_self_route(int B, int N, int K, int method, int has_prior, int scratch_ok);
+
 /* Names and byte offsets (address order) of the buffers geoa3_pointnet_forward / _backward keep in their workspace:
  * tools/iteration_replay_soak.py attributes a run-to-run difference to the kernel that wrote it.  Returns the number
  * of buffers (names[i] are static strings). */

@@ -60,6 +60,13 @@ def main():
     # the attack's regime: a stale table (last iteration's, here the clean cloud's) as the radius
     res["knn_grid_stale_us"] = timeit(lambda: ops.knn_self_planar(far, k + 1, knn_ori, scratch, method=2), a.iters)
     res["knn_slab_stale_us"] = timeit(lambda: ops.knn_self_planar(far, k + 1, knn_ori, scratch, method=1), a.iters)
+    # the position-list slab kernel for long lists / large clouds (knn_slabp_kernel<56, true>): method 4 at K = 33, N = 4096
+    u4 = torch.randn(B, 3, 4096, generator=g)
+    ori4 = (u4 / u4.norm(dim=1, keepdim=True)).cuda().contiguous()
+    adv4 = (ori4 + 0.01 * torch.randn(B, 3, 4096, generator=g).cuda()).contiguous()
+    _, knn4 = ops.knn_planar(ori4, ori4, 33)
+    scratch4 = ops.knn_self_scratch(B, 4096, adv4.device)
+    res["knn_slabp56_n4096_k33_us"] = timeit(lambda: ops.knn_self_planar(adv4, 33, knn4, scratch4, method=4), a.iters)
     kap = ops.kappa(ori, nrm, knn_ori)
     res["kappa_us"] = timeit(lambda: ops.kappa(ori, nrm, knn_ori), a.iters)
     d_ao, i_ao, d_oa, i_oa = ops.nn1_pair(adv, ori)
