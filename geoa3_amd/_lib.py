@@ -77,6 +77,7 @@ SIGNATURES = {
     "geoa3_knn_self": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
     "geoa3_kappa": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_geo_loss_grad": (C.c_int, [C.POINTER(GeoArgs), vp]),
+    "geoa3_geo_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "geoa3_pointnet_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "geoa3_pointnet_forward": (C.c_int, [C.POINTER(PointNetWeights), vp, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_pointnet_backward": (C.c_int, [C.POINTER(PointNetWeights), vp, vp, C.c_int, C.c_int, vp, vp, vp]),
@@ -153,6 +154,9 @@ SIGNATURES = {
                                                         C.POINTER(C.c_int64), C.c_int]),
     "geoa3_debug_grid_nn1_pair": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp]),
     "geoa3_debug_knn_self_route": (C.c_int, [C.c_int] * 6),
+    "geoa3_debug_geo_route": (C.c_int, [C.POINTER(GeoArgs)]),
+    "geoa3_debug_geo_wide_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "geoa3_debug_geo_wide": (C.c_int, [C.POINTER(GeoArgs), C.c_int, vp]),
     "geoa3_debug_fc": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "geoa3_debug_conv_cm": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "geoa3_debug_wide_bwd_conv": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int,
@@ -172,7 +176,7 @@ _lib = None
 
 ENOSUPPORT = -3   # GEOA3_ENOSUPPORT
 PN2_CONTRACT = 1   # GEOA3_PN2_CONTRACT
-ABI_VERSION = 605  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
+ABI_VERSION = 606  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
 
 
 class Geoa3Error(RuntimeError):

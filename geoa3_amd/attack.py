@@ -165,7 +165,10 @@ class AttackRunner:
             self.uni_contract = getattr(net, "ext_contract", None)
         self.geo_out["grad"] = t["g_geo"]
         # clouds of 1025..4096 points (or k > 32): the records of the fixed-point objective kernel (geoa3_geo_args.scratch)
-        self.geo_scratch = ops.geo_scratch(b, ne, device) if ((1024 < ne or self.k > 32) and ne <= 4096 and self.use_curv) else None
+        # 5840..8192 points: the records and partial sums of the two-pass kernels, with or without the curvature term
+        self.geo_scratch = (ops.geo_scratch(b, ne, device, self.k)
+                            if (((1024 < ne or self.k > 32) and ne <= 4096 and self.use_curv)
+                                or ops.GEO_WIDE_MIN_N <= ne <= 8192) else None)
         if self.use_curv:
             t["knn"] = [torch.zeros(b, ne, self.k + 1, **i32) for _ in range(2)]
             t["knn_d"] = z(b, ne, self.k + 1)

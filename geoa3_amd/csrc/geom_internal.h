@@ -20,3 +20,10 @@ int geoa3_launch_grid_nn1(const float* a, const float* r, int B, int Na, int Nr,
 // every query of every instance, clouds of any size.
 int geoa3_launch_nn1_filter(const float* a, const float* r, int B, int Na, int Nr, const int32_t* prior_ar,
                             const int32_t* prior_ra, float* d_ar, int32_t* i_ar, float* d_ra, int32_t* i_ra, hipStream_t s);
+// The geometric objective for clouds too large for one workgroup's LDS (geom_loss_wide.hip; chosen by geoa3_geo_loss_grad,
+// geom_loss.hip): 64 <= N <= GEO_WIDE_MAX_N, scratch of geo_wide_scratch_bytes(B, N) bytes.  `ranges`: owner ranges per
+// instance (geo_wide_ranges(N): the fewest that fit LDS, 0 = none does); GEOA3_ENOSUPPORT when that many do not fit.
+constexpr int GEO_WIDE_MAX_N = 8192;
+size_t geo_wide_scratch_bytes(int B, int N);
+int geo_wide_ranges(int N);
+int geo_wide_launch(const geoa3_geo_args* a, int ranges, hipStream_t s);

@@ -7,10 +7,10 @@
 #include <type_traits>
 #include "common.h"
 #include "profile.h"
+#include "geom_internal.h"
+#include "geom_loss_fix.h"
 
 namespace {
-
-constexpr float NORM_EPS = 1e-12f;  // Lib/utility.py:30 (_normalize eps)
 
 // | < normalize(q - p), n > | summed over the k neighbours listed in nb[1..k] (nb[0] is dropped).
 template <typename Fetch>
@@ -65,13 +65,6 @@ __global__ __launch_bounds__(LDS ? 1024 : 256) void kappa_kernel(const float* __
 constexpr int GEO_BLOCK = 1024;
 constexpr int GEO_WAVES = GEO_BLOCK / GEOA3_WAVE;
 
-struct MaxIdx {
-  float v;
-  int i;
-};
-__device__ __forceinline__ MaxIdx better(MaxIdx a, MaxIdx b) {  // larger value, then lower index
-  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
 
 // DET: the gradient is accumulated by the OWNER of every point in a fixed order (own terms, then the contributions it
 // receives from other points sorted by their source) instead of with LDS float atomics, whose order is free: bit-for-
@@ -485,100 +478,6 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
 
 
 // ------------------------------------------------------------------------------------------
-// Order-free accumulation of gradient terms: 64-bit FIXED POINT at two scales, chosen per instance.
-//
-// Integer addition is associative, so sums of converted terms do not depend on who adds them in which order (LDS integer
-// atomics): deterministic and batch-independent without reverse lists.  Round 4 used ONE fixed scale (2^-44 per unit, every
-// term clamped silently at 2^18): right for the attack loop's magnitudes, wrong for a caller-supplied dkappa, for loss
-// weights far from 1 and for near-coincident pairs (a pair term is ~ 2 dk / r).  Now, with X = the instance's largest
-// coefficient (2 w_curv / (N k) or max |dkappa| / k; the Chamfer coefficients) and Ex = ceil(log2 X):
-//   fine    unit 2^(Ex - 40), terms up to 2^(Ex + 10):  4096 of them still fit 63 bits; X-relative precision 2^-40;
-//   coarse  unit 2^(Ex - 16), terms up to 2^(Ex + 34):  pairs down to r ~ 1e-10 at the largest coefficient -- they are
-//           rare, so their sums live in a small hash pool in LDS keyed by the destination point;
-//   beyond that (or NaN, or a full pool): the destination's gradient is written as NaN -- loud, never a silent clamp.
-// The result is fine * 2^(Ex - 40) + coarse * 2^(Ex - 16) in fp32.
-// ------------------------------------------------------------------------------------------
-struct GeoFix {
-  float to_f, to_c, from_f, from_c, lim_f, lim_c;
-};
-__device__ __forceinline__ float geo_pow2(int k) { return __uint_as_float((unsigned)(k + 127) << 23); }   // -126 <= k <= 127
-__device__ __forceinline__ GeoFix geo_fix_make(float X) {
-  int Ex = (int)((__float_as_uint(X) >> 23) & 0xffu) - 126;        // X < 2^Ex (X = m 2^Ex, 0.5 <= m < 1)
-  Ex = Ex < -80 ? -80 : (Ex > 60 ? 60 : Ex);                        // (X = 0, denormal or absurd: any scale will do)
-  GeoFix f;
-  f.to_f = geo_pow2(40 - Ex);
-  f.to_c = geo_pow2(16 - Ex);
-  f.from_f = geo_pow2(Ex - 40);
-  f.from_c = geo_pow2(Ex - 16);
-  f.lim_f = geo_pow2(Ex + 10);
-  f.lim_c = geo_pow2(Ex + 34);
-  return f;
-}
-__device__ __forceinline__ unsigned long long geo_fix_conv(float v, float mul) {
-  return (unsigned long long)__float2ll_rn(v * mul);
-}
-// hash pool of destinations with coarse sums: key [cap] (-1 = empty), acc [cap][W] 64-bit words
-struct GeoPool {
-  int* key;
-  unsigned long long* acc;
-  int cap;   // a power of two
-};
-__device__ __forceinline__ int geo_pool_find(const GeoPool& P, int q, bool insert) {
-  unsigned h = ((unsigned)q * 0x9E3779B1u) >> 8;
-  for (int step = 0; step < P.cap; ++step) {
-    const int s = (int)((h + (unsigned)step) & (unsigned)(P.cap - 1));
-    int kk = P.key[s];
-    if (kk == q) return s;
-    if (kk == -1) {
-      if (!insert) return -1;
-      kk = atomicCAS(&P.key[s], -1, q);
-      if (kk == -1 || kk == q) return s;
-    }
-  }
-  return -1;
-}
-__device__ __forceinline__ void geo_mark_bad(unsigned* s_bad, int q) { atomicOr(&s_bad[q >> 5], 1u << (q & 31)); }
-// one gradient term of destination q: into the per-point fine sums (planes of N, or null: everything through the pool,
-// words 0-2 fine / 3-5 coarse), the pool's coarse sums, or the sticky NaN flags
-template <int W>
-__device__ __forceinline__ void geo_fix_add(const GeoFix& F, unsigned long long* fine, int N, const GeoPool& P, unsigned* s_bad,
-                                            int q, float x, float y, float z) {
-  const float m = fmaxf(fmaxf(fabsf(x), fabsf(y)), fabsf(z));
-  if (m <= F.lim_f) {
-    if (W == 3) {
-      atomicAdd(&fine[q], geo_fix_conv(x, F.to_f));
-      atomicAdd(&fine[N + q], geo_fix_conv(y, F.to_f));
-      atomicAdd(&fine[2 * N + q], geo_fix_conv(z, F.to_f));
-    } else {
-      const int s = geo_pool_find(P, q, true);
-      if (s < 0) return geo_mark_bad(s_bad, q);
-      atomicAdd(&P.acc[s * W + 0], geo_fix_conv(x, F.to_f));
-      atomicAdd(&P.acc[s * W + 1], geo_fix_conv(y, F.to_f));
-      atomicAdd(&P.acc[s * W + 2], geo_fix_conv(z, F.to_f));
-    }
-  } else if (m <= F.lim_c) {
-    const int s = geo_pool_find(P, q, true);
-    if (s < 0) return geo_mark_bad(s_bad, q);
-    atomicAdd(&P.acc[s * W + W - 3], geo_fix_conv(x, F.to_c));
-    atomicAdd(&P.acc[s * W + W - 2], geo_fix_conv(y, F.to_c));
-    atomicAdd(&P.acc[s * W + W - 1], geo_fix_conv(z, F.to_c));
-  } else {
-    geo_mark_bad(s_bad, q);      // out of range or NaN
-  }
-}
-constexpr int GEO_POOL_CAP = 128;                                     // geo_fused_kernel: overflowed rows (fine + coarse sums)
-constexpr size_t GEO_POOL_BYTES = GEO_POOL_CAP * (4 + 6 * 8) + 8;     // keys + sums + alignment
-constexpr int GB_POOL_CAP = 256;                                      // geo_big_kernel: destinations with coarse terms
-// the instance's largest coefficient: max |dkappa| / k over the block (dkappa mode) or the loss's analytic bound (kappa is a
-// mean of |cosines|: |kappa_adv - kappa_ori| <= 1), and the Chamfer coefficients
-__device__ __forceinline__ float geo_coef_bound(const geoa3_geo_args& A, int N, int Nr, float block_max_dkappa) {
-  const float k = (float)(A.k > 0 ? A.k : 1);
-  float X = A.dkappa ? block_max_dkappa / k : fabsf(A.w_curv) * 2.0f / ((float)N * k);
-  X = fmaxf(X, fabsf(A.w_dis) * 2.0f / (float)(N < Nr ? N : Nr));
-  return X;
-}
-
-// ------------------------------------------------------------------------------------------
 // Deterministic objective for clouds of at most 1024 points (the default there): one 1024-thread workgroup per instance
 // as above, but every (centre, neighbour) PAIR a lane and no dependent chain longer than one round trip.
 //
@@ -602,17 +501,6 @@ __device__ __forceinline__ float geo_coef_bound(const geoa3_geo_args& A, int N, 
 // ------------------------------------------------------------------------------------------
 constexpr int GEO_T = 1024;
 
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {   // sum over aligned groups of G lanes, in every lane of the group
-  if (G >= 2) v += dpp_f32<0xB1, 0xF>(v, 0.f);           // lane ^ 1
-  if (G >= 4) v += dpp_f32<0x4E, 0xF>(v, 0.f);           // lane ^ 2
-  if (G >= 8) v += dpp_f32<0x141, 0xF>(v, 0.f);          // row_half_mirror
-  if (G >= 16) v += dpp_f32<0x140, 0xF>(v, 0.f);         // row_mirror
-  if (G >= 32) v += __shfl_xor(v, 16, 64);
-  if (G >= 64) v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
 // ascending bitonic sort of W keys held in registers (fully unrolled: indices are compile-time constants)
 template <int W>
 __device__ __forceinline__ void geo_sort_regs(int (&v)[W]) {
@@ -632,44 +520,6 @@ __device__ __forceinline__ void geo_sort_regs(int (&v)[W]) {
       }
     }
   }
-}
-
-// d |<normalize(q - p), n>| * dk / d q for the pair (centre p with normal n and coefficient dk, neighbour q): what the
-// centre subtracts from its own gradient and q adds to its
-// The pair kernel is bound by VALU issue on the one CU that holds an instance (~100 instructions per pair term, a third
-// of them the IEEE sqrt / division sequences): v_sqrt_f32 and v_rcp_f32 (1 ulp each) take 8 us off 51 (250 instances).
-// Two ulp per pair term is far inside the parity bars (values rtol 2e-5, gradients 1e-4; the summation order already
-// differs from torch's); -DGEOA3_GEO_IEEE restores the correctly rounded forms.
-#ifdef GEOA3_GEO_IEEE
-#define GEO_SQRT(x) sqrtf(x)
-#define GEO_RCP(x) (1.0f / (x))
-#else
-#define GEO_SQRT(x) __builtin_amdgcn_sqrtf(x)
-#define GEO_RCP(x) __builtin_amdgcn_rcpf(x)
-#endif
-// (The multiply-adds are spelled out and contraction is OFF inside: the overflowed-row path forms a row's terms at two
-// call sites -- the pair lane in phase 1, the owner in phase 2 -- whose sums must agree bit for bit whichever of them
-// converts a given term; left to -ffp-contract=fast each inlined copy is fused as its surroundings suggest.)
-__device__ __forceinline__ void geo_pair_grad(float px, float py, float pz, float nx, float ny, float nz, float dk, float qx,
-                                              float qy, float qz, float& dvx, float& dvy, float& dvz, float& t_out) {
-#pragma clang fp contract(off)
-  const float vx = qx - px, vy = qy - py, vz = qz - pz;
-  const float r = GEO_SQRT(__builtin_fmaf(vz, vz, __builtin_fmaf(vy, vy, vx * vx)));
-  const float inv = GEO_RCP(fmaxf(r, NORM_EPS));
-  const float ux = vx * inv, uy = vy * inv, uz = vz * inv;
-  const float t = __builtin_fmaf(uz, nz, __builtin_fmaf(uy, ny, ux * nx));
-  const float sg = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
-  const float c = dk * sg * inv;
-  if (r >= NORM_EPS) {  // d(v/|v|)/dv = (I - u u^T)/|v|
-    dvx = c * __builtin_fmaf(-t, ux, nx);
-    dvy = c * __builtin_fmaf(-t, uy, ny);
-    dvz = c * __builtin_fmaf(-t, uz, nz);
-  } else {              // clamp active: v/eps, the norm path carries no gradient
-    dvx = c * nx;
-    dvy = c * ny;
-    dvz = c * nz;
-  }
-  t_out = t;
 }
 
 template <int G>
@@ -1403,27 +1253,39 @@ extern "C" int geoa3_kappa(const float* pc, const float* normal, const int32_t* 
   return GEOA3_OK;
 }
 
-extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
-  if (!a || !a->adv || !a->ori || a->B <= 0 || a->N <= 0 || a->Nr < 0) return GEOA3_EINVAL;
-  if (a->dis_type == 2 && a->Nr > 0 && a->Nr != a->N) return GEOA3_EINVAL;  // norm_l2_loss needs equal sizes
-  if (a->dis_type == 1 && (!a->d_ao || !a->i_ao)) return GEOA3_EINVAL;
-  if (a->w_hd != 0.f && (!a->d_ao || !a->i_ao)) return GEOA3_EINVAL;
-  if ((a->w_curv != 0.f || a->dkappa) && (!a->knn_adv || !a->normal_ori || !a->i_ao || a->k <= 0))
-    return GEOA3_EINVAL;
-  if (a->w_curv != 0.f && !a->dkappa && !a->kappa_ori) return GEOA3_EINVAL;
+// ------------------------------------------------------------------------------------------
+// Which kernel a call takes, as a host function of the sizes and of which buffers are given (geoa3_debug_geo_route shows
+// it to tests/test_geo_route.py), with what the launch needs.
+// ------------------------------------------------------------------------------------------
+namespace {
+struct GeoPlan {
+  int route;          // GEOA3_GEO_ROUTE_*, or GEOA3_EINVAL
+  int G, S, R, C;     // fused: lanes per centre, owner ranges, their length, row capacity; big: G
+  size_t lds;
+  int rcap, nrm_in;   // the one-workgroup kernel with lists
+};
+
+GeoPlan geo_plan(const geoa3_geo_args* a) {
+  GeoPlan p{};
+  p.route = GEOA3_EINVAL;
+  if (!a || !a->adv || !a->ori || a->B <= 0 || a->N <= 0 || a->Nr < 0) return p;
+  if (a->dis_type == 2 && a->Nr > 0 && a->Nr != a->N) return p;  // norm_l2_loss needs equal sizes
+  if (a->dis_type == 1 && (!a->d_ao || !a->i_ao)) return p;
+  if (a->w_hd != 0.f && (!a->d_ao || !a->i_ao)) return p;
+  if ((a->w_curv != 0.f || a->dkappa) && (!a->knn_adv || !a->normal_ori || !a->i_ao || a->k <= 0)) return p;
+  if (a->w_curv != 0.f && !a->dkappa && !a->kappa_ori) return p;
   // what the choice of kernel rests on, derived once (the kernels' do_curv / two_side / Nr)
   const int N = a->N, Nr = a->Nr > 0 ? a->Nr : a->N;
   const bool do_curv = (a->w_curv != 0.f || a->dkappa) && a->knn_adv;
   const bool two_side = a->dis_type == 1 && !a->single_side && a->d_oa != nullptr;
   const bool ordered = a->deterministic || !a->grad;   // a reproducible gradient, or none at all
-  hipStream_t s = geoa3_stream(stream);
 
   // ---- 1. the pair-parallel kernel, if the instance fits: the cloud, its normals, coefficients and own terms (10 N floats),
   // row lengths, and one row of C source ids per point; rows of 2 (k + clean points per point) + 16 ids (in-degrees of a
   // k-NN graph concentrate around k), at least 32, at most what fits
   // (k > 32 with a scratch buffer: the fixed-point kernel below -- geo_fused_kernel<64> carries 272 bytes of scratch per lane)
   if (ordered && N <= GEO_T && a->k <= 64 && !(a->k > 32 && a->scratch && do_curv)) {
-    if (two_side && !a->i_oa) return GEOA3_EINVAL;
+    if (two_side && !a->i_oa) return p;
     const int per = (do_curv ? a->k : 0) + (two_side ? (Nr + N - 1) / N : 0);
     const size_t fixed = ((size_t)12 * N + 16 * 5 + 4) * sizeof(float);
     const size_t room = 160 * 1024 - 256 - fixed - GEO_POOL_BYTES;
@@ -1436,56 +1298,40 @@ extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
     const int Cfit = (int)(room / ((size_t)R * sizeof(uint16_t))) - 1;
     if (C > Cfit) C = Cfit;
     if (N + Nr < 65535 && C >= 32 && 2 * C >= 3 * per + 16) {
-      const size_t lds = fixed + (size_t)R * (C + 1) * sizeof(uint16_t) + GEO_POOL_BYTES;
-      int G = 1;
-      while (G < a->k && do_curv) G *= 2;
-      geoa3_prof_begin(GEOA3_PROF_GEO, s);
-#define GEOA3_FUSED_CASE(GG)                                                                                           \
-  if (G == GG) {                                                                                                       \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_fused_kernel<GG>),                                     \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                   \
-    hipLaunchKernelGGL(geo_fused_kernel<GG>, dim3(a->B, S), dim3(GEO_T), lds, s, *a, C, R);                                  \
-  }
-      GEOA3_FUSED_CASE(1)
-      GEOA3_FUSED_CASE(2)
-      GEOA3_FUSED_CASE(4)
-      GEOA3_FUSED_CASE(8)
-      GEOA3_FUSED_CASE(16)
-      GEOA3_FUSED_CASE(32)
-      GEOA3_FUSED_CASE(64)
-#undef GEOA3_FUSED_CASE
-      geoa3_prof_end(GEOA3_PROF_GEO, s);
-      GEOA3_CHECK_LAUNCH();
-      return GEOA3_OK;
+      p.route = GEOA3_GEO_ROUTE_FUSED;
+      p.S = S;
+      p.R = R;
+      p.C = C;
+      p.lds = fixed + (size_t)R * (C + 1) * sizeof(uint16_t) + GEO_POOL_BYTES;
+      p.G = 1;
+      while (p.G < a->k && do_curv) p.G *= 2;
+      return p;
     }
   }
   // ---- 2. else the pair-parallel kernel with fixed-point sums (see geo_big_kernel), given the caller's scratch buffer
   if (ordered && a->scratch && do_curv && (N > GEO_T || a->k > 32) && N <= 4096 && a->k <= 64) {
-    if (two_side && !a->i_oa) return GEOA3_EINVAL;
-    int G = 1;
-    while (G < a->k) G *= 2;
-    if (G < 16) G = 16;
-    float4* ctr = reinterpret_cast<float4*>(a->scratch);
-    const size_t lds2 = (size_t)36 * N + (16 * 5 + 4) * sizeof(float) + 8 + GB_POOL_CAP * (3 * 8 + 4) + ((size_t)(N + 31) / 32) * 4;
-    geoa3_prof_begin(GEOA3_PROF_GEO, s);
-    hipLaunchKernelGGL(geo_big_gather_kernel, dim3((N + 255) / 256, a->B), dim3(256), 0, s, *a, ctr);
-#define GEOA3_BIG_CASE(GG)                                                                                             \
-  if (G == GG) {                                                                                                       \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_big_kernel<GG>),                                       \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                  \
-    hipLaunchKernelGGL(geo_big_kernel<GG>, dim3(a->B), dim3(GB_T), lds2, s, *a, ctr);                                  \
-  }
-    GEOA3_BIG_CASE(16)
-    GEOA3_BIG_CASE(32)
-    GEOA3_BIG_CASE(64)
-#undef GEOA3_BIG_CASE
-    geoa3_prof_end(GEOA3_PROF_GEO, s);
-    GEOA3_CHECK_LAUNCH();
-    return GEOA3_OK;
+    if (two_side && !a->i_oa) return p;
+    p.route = GEOA3_GEO_ROUTE_BIG;
+    p.G = 1;
+    while (p.G < a->k) p.G *= 2;
+    if (p.G < 16) p.G = 16;
+    p.lds = (size_t)36 * N + (16 * 5 + 4) * sizeof(float) + 8 + GB_POOL_CAP * (3 * 8 + 4) + ((size_t)(N + 31) / 32) * 4;
+    return p;
   }
   // ---- 3. else the one-workgroup kernel: owner lists where they fit beside the cloud, LDS float atomics otherwise
   const size_t base = ((size_t)7 * N + GEO_WAVES * 5 + 4) * sizeof(float);
-  if (base > 160 * 1024) return GEOA3_ENOSUPPORT;  // N <= ~5800 points per instance
+  if (base > 160 * 1024) {   // N >= 5840 points per instance
+    // ---- 4. the two-pass kernels of geom_loss_wide.hip: up to 8192 points, given the caller's scratch buffer
+    p.route = GEOA3_GEO_ROUTE_REFUSED;
+    if (!a->scratch || N > GEO_WIDE_MAX_N || (do_curv && a->k > 64)) return p;
+    if (two_side && !a->i_oa) {
+      p.route = GEOA3_EINVAL;
+      return p;
+    }
+    p.S = geo_wide_ranges(N);
+    if (p.S > 0) p.route = GEOA3_GEO_ROUTE_WIDE;
+    return p;
+  }
   const size_t idx = ((size_t)N + 1) * sizeof(int);
   // (clouds whose reverse lists do not fit beside the cloud -- N > ~4800 -- take the atomic kernel: same values, free
   // summation order, documented in geoa3_hip.h)
@@ -1498,22 +1344,91 @@ extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
     size_t rcap = (cap - base - idx - (nrm_in ? nrm : 0)) / sizeof(int);
     if (rcap > all) rcap = all;
     if (rcap < 1) rcap = 1;
-    const size_t lds = base + idx + (nrm_in ? nrm : 0) + rcap * sizeof(int);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_loss_grad_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    geoa3_prof_begin(GEOA3_PROF_GEO, s);
-    hipLaunchKernelGGL(geo_loss_grad_kernel<true>, dim3(a->B), dim3(GEO_BLOCK), lds, s, *a, (int)rcap, nrm_in);
-    geoa3_prof_end(GEOA3_PROF_GEO, s);
-    GEOA3_CHECK_LAUNCH();
-    return GEOA3_OK;
+    p.route = GEOA3_GEO_ROUTE_LISTS;
+    p.rcap = (int)rcap;
+    p.nrm_in = nrm_in;
+    p.lds = base + idx + (nrm_in ? nrm : 0) + rcap * sizeof(int);
+    return p;
   }
-  const size_t lds = base;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_loss_grad_kernel<false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  geoa3_prof_begin(GEOA3_PROF_GEO, s);
-  hipLaunchKernelGGL(geo_loss_grad_kernel<false>, dim3(a->B), dim3(GEO_BLOCK), lds, s, *a, 0, 0);
-  geoa3_prof_end(GEOA3_PROF_GEO, s);
+  p.route = GEOA3_GEO_ROUTE_ATOMICS;
+  p.lds = base;
+  return p;
+}
+}  // namespace
+
+extern "C" int geoa3_debug_geo_route(const geoa3_geo_args* a) { return geo_plan(a).route; }
+
+extern "C" int64_t geoa3_geo_scratch_bytes(int B, int N, int k) {
+  (void)k;
+  if (B <= 0 || N <= 0) return 0;
+  return N <= 4096 ? (int64_t)16 * B * N : (int64_t)geo_wide_scratch_bytes(B, N);
+}
+
+extern "C" int geoa3_geo_loss_grad(const geoa3_geo_args* a, void* stream) {
+  const GeoPlan p = geo_plan(a);
+  hipStream_t s = geoa3_stream(stream);
+  switch (p.route) {
+    case GEOA3_GEO_ROUTE_FUSED:
+      geoa3_prof_begin(GEOA3_PROF_GEO, s);
+#define GEOA3_FUSED_CASE(GG)                                                                                           \
+  if (p.G == GG) {                                                                                                     \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_fused_kernel<GG>),                                     \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);                                 \
+    hipLaunchKernelGGL(geo_fused_kernel<GG>, dim3(a->B, p.S), dim3(GEO_T), p.lds, s, *a, p.C, p.R);                    \
+  }
+      GEOA3_FUSED_CASE(1)
+      GEOA3_FUSED_CASE(2)
+      GEOA3_FUSED_CASE(4)
+      GEOA3_FUSED_CASE(8)
+      GEOA3_FUSED_CASE(16)
+      GEOA3_FUSED_CASE(32)
+      GEOA3_FUSED_CASE(64)
+#undef GEOA3_FUSED_CASE
+      geoa3_prof_end(GEOA3_PROF_GEO, s);
+      break;
+    case GEOA3_GEO_ROUTE_BIG: {
+      float4* ctr = reinterpret_cast<float4*>(a->scratch);
+      geoa3_prof_begin(GEOA3_PROF_GEO, s);
+      hipLaunchKernelGGL(geo_big_gather_kernel, dim3((a->N + 255) / 256, a->B), dim3(256), 0, s, *a, ctr);
+#define GEOA3_BIG_CASE(GG)                                                                                             \
+  if (p.G == GG) {                                                                                                     \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_big_kernel<GG>),                                       \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);                                 \
+    hipLaunchKernelGGL(geo_big_kernel<GG>, dim3(a->B), dim3(GB_T), p.lds, s, *a, ctr);                                 \
+  }
+      GEOA3_BIG_CASE(16)
+      GEOA3_BIG_CASE(32)
+      GEOA3_BIG_CASE(64)
+#undef GEOA3_BIG_CASE
+      geoa3_prof_end(GEOA3_PROF_GEO, s);
+      break;
+    }
+    case GEOA3_GEO_ROUTE_LISTS:
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_loss_grad_kernel<true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      geoa3_prof_begin(GEOA3_PROF_GEO, s);
+      hipLaunchKernelGGL(geo_loss_grad_kernel<true>, dim3(a->B), dim3(GEO_BLOCK), p.lds, s, *a, p.rcap, p.nrm_in);
+      geoa3_prof_end(GEOA3_PROF_GEO, s);
+      break;
+    case GEOA3_GEO_ROUTE_ATOMICS:
+      if (p.lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(geo_loss_grad_kernel<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      geoa3_prof_begin(GEOA3_PROF_GEO, s);
+      hipLaunchKernelGGL(geo_loss_grad_kernel<false>, dim3(a->B), dim3(GEO_BLOCK), p.lds, s, *a, 0, 0);
+      geoa3_prof_end(GEOA3_PROF_GEO, s);
+      break;
+    case GEOA3_GEO_ROUTE_WIDE: {
+      geoa3_prof_begin(GEOA3_PROF_GEO, s);
+      const int rc = geo_wide_launch(a, p.S, s);
+      geoa3_prof_end(GEOA3_PROF_GEO, s);
+      return rc;
+    }
+    case GEOA3_GEO_ROUTE_REFUSED:
+      return GEOA3_ENOSUPPORT;
+    default:
+      return GEOA3_EINVAL;
+  }
   GEOA3_CHECK_LAUNCH();
   return GEOA3_OK;
 }

@@ -114,19 +114,25 @@ def kappa(pc: Tensor, normal: Tensor, knn_idx: Tensor, nn_idx: Optional[Tensor] 
     return out
 
 
-def geo_scratch(B: int, N: int, device) -> Tensor:
-    """geoa3_geo_args.scratch for B clouds of N points (16 bytes per point)."""
-    return torch.empty(B * N * 16, dtype=torch.uint8, device=device)
+GEO_WIDE_MIN_N = 5840   # the first cloud no single workgroup holds: geoa3_geo_loss_grad needs a scratch buffer from here on
+
+
+def geo_scratch(B: int, N: int, device, k: int = 0) -> Tensor:
+    """geoa3_geo_args.scratch for B clouds of N points (geoa3_geo_scratch_bytes: 16 bytes per point up to 4096 points)."""
+    return torch.empty(int(_lib.load().geoa3_geo_scratch_bytes(B, N, k)), dtype=torch.uint8, device=device)
 
 
 def geo_loss_grad(adv: Tensor, ori: Tensor, *, normal_ori=None, kappa_ori=None, d_ao=None, i_ao=None, d_oa=None,
                   i_oa=None, knn_adv=None, dkappa=None, k: int = 0, dis_type: int = 1, single_side: bool = False,
                   w_dis: float = 1.0, w_hd: float = 0.0, w_curv: float = 0.0, want_grad: bool = True,
                   want_kappa: bool = False, out: Optional[dict] = None, deterministic: bool = True,
-                  scratch: Optional[Tensor] = None) -> dict:
+                  scratch: Optional[Tensor] = None, wide_ranges: Optional[int] = None) -> dict:
     """The fused geometric objective (Attacker/geoA3_attack.py:131-166) and d constrain / d adv.
     deterministic (default): every point's gradient is summed by its owner in a fixed order -- bit-for-bit reproducible
-    and independent of the rest of the batch; False: LDS float atomics (free summation order)."""
+    and independent of the rest of the batch; False: LDS float atomics (free summation order).  Clouds of up to 8192
+    points; from 5840 points on the sums are order-free whatever `deterministic` says.
+    wide_ranges (tests, tools): the two-pass kernels of those sizes on this cloud, 64..8192 points, with that many owner
+    ranges per instance (geoa3_debug_geo_wide; 0 = the dispatcher's choice)."""
     B, _, N = adv.shape
     dev = adv.device
     o = out if out is not None else {}
@@ -137,8 +143,12 @@ def geo_loss_grad(adv: Tensor, ori: Tensor, *, normal_ori=None, kappa_ori=None, 
         o["grad"] = torch.empty(B, 3, N, device=dev, dtype=torch.float32)
     if want_kappa and "kappa_adv" not in o:
         o["kappa_adv"] = torch.empty(B, N, device=dev, dtype=torch.float32)
-    if scratch is None and (deterministic or not want_grad) and (1024 < N or k > 32) and N <= 4096 and knn_adv is not None:
-        scratch = geo_scratch(B, N, dev)      # (callers in a loop hand over their own: AttackRunner)
+    if wide_ranges is not None:
+        scratch = torch.empty(int(_lib.load().geoa3_debug_geo_wide_scratch_bytes(B, N)), dtype=torch.uint8, device=dev)
+    elif scratch is None and (deterministic or not want_grad) and (1024 < N or k > 32) and N <= 4096 and knn_adv is not None:
+        scratch = geo_scratch(B, N, dev, k)   # (callers in a loop hand over their own: AttackRunner)
+    elif scratch is None and GEO_WIDE_MIN_N <= N <= 8192:   # the two-pass kernels, with or without the curvature term
+        scratch = geo_scratch(B, N, dev, k)
     elif scratch is False:                    # tests: the one-workgroup kernel
         scratch = None
     a = GeoArgs(adv=_p(adv, torch.float32), ori=_p(ori, torch.float32), normal_ori=_p(normal_ori),
@@ -150,7 +160,10 @@ def geo_loss_grad(adv: Tensor, ori: Tensor, *, normal_ori=None, kappa_ori=None, 
                 constrain=_p(o["constrain"]), kappa_adv=_p(o.get("kappa_adv")) if want_kappa else None,
                 grad=_p(o["grad"]) if want_grad else None, deterministic=int(bool(deterministic)),
                 scratch=_p(scratch))
-    check(_lib.load().geoa3_geo_loss_grad(C.byref(a), _stream()), "geoa3_geo_loss_grad")
+    if wide_ranges is not None:
+        check(_lib.load().geoa3_debug_geo_wide(C.byref(a), int(wide_ranges), _stream()), "geoa3_debug_geo_wide")
+    else:
+        check(_lib.load().geoa3_geo_loss_grad(C.byref(a), _stream()), "geoa3_geo_loss_grad")
     return o
 
 

@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 605
+#define GEOA3_ABI_VERSION 606
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -144,19 +144,31 @@ typedef struct geoa3_geo_args {
    * Clouds of at most 1024 points take the pair-parallel kernel (a lane per (centre, neighbour) pair, reverse lists as
    * fixed-capacity rows in LDS, rows sorted in registers; a row beyond its ~50 slots -- a dense cluster, a hub of the
    * K-NN graph -- through 64-bit fixed-point sums in a small pool, order-free); 1025..4096 points with `scratch`: the
-   * pair-parallel kernel with fixed-point sums; otherwise up to ~4800 points the one-workgroup kernel with LDS reverse lists; beyond (up to ~5800)
-   * the sums fall back to LDS float atomics (free order) whatever this flag says. */
+   * pair-parallel kernel with fixed-point sums; otherwise up to ~4800 points the one-workgroup kernel with LDS reverse lists; beyond (up to 5839)
+   * the sums fall back to LDS float atomics (free order) whatever this flag says.  5840..8192 points need `scratch` and take
+   * the two-pass kernels with fixed-point sums, order-free whatever this flag says; without `scratch`, or beyond 8192
+   * points, the call returns GEOA3_ENOSUPPORT. */
   int32_t deterministic;
-  /* optional workspace of 16 * B * N bytes (one float4 record per point).  Given, clouds of 1025..4096 points (and smaller
+  /* optional workspace of geoa3_geo_scratch_bytes(B, N, k) bytes: 16 * B * N (one float4 record per point) up to 4096 points,
+   * the records plus the partial loss sums of every 1024 points beyond.  Given, clouds of 1025..4096 points (and smaller
    * ones with k > 32) with the curvature term take the pair-parallel kernel with 64-bit fixed-point gradient sums (geo_big_kernel: order-free and
    * therefore reproducible; the neighbour table is read once); NULL = the one-workgroup kernel.  Same values to rounding.
    * The fixed-point sums take two power-of-two scales per instance from its largest coefficient X (2 w_curv / (N k) or
    * max |dkappa| / k, and the Chamfer coefficients): terms up to 2^10 X at 2^-40 X per unit, terms up to 2^34 X (pairs down
    * to ~1e-10 apart) at 2^-16 X through a pool of 256 destinations.  A term beyond that, a NaN, or a full pool writes NaN
-   * into the gradient of the destination point -- there is no silent saturation. */
+   * into the gradient of the destination point -- there is no silent saturation.
+   * Clouds of 5840..8192 points (what no single workgroup's LDS holds; required there, with or without the curvature term):
+   * pass A, a workgroup per 1024 centres, writes kappa_adv, the records (normal, pair coefficient) and partial loss sums;
+   * pass B, a workgroup per owner range of ceil(N / S) points (S = the fewest ranges that fit LDS: 2 up to ~7400 points, 4
+   * beyond), streams table and records once and keeps the 64-bit sums of its own range.  Same two scales, with both limits
+   * halved (2^9 X and 2^33 X; once more per doubling of N + Nr beyond 16384) so that N + Nr terms cannot wrap a sum.  The
+   * gradient depends on neither S nor the batch; the loss values are summed per 1024 points, then in that order.
+   * Clouds of 4097..5839 points take the one-workgroup kernel whether `scratch` is given or not. */
   void* scratch;
 } geoa3_geo_args;
 int geoa3_geo_loss_grad(const geoa3_geo_args* args, void* stream);
+/* bytes of geoa3_geo_args.scratch for B clouds of N points (k: the neighbours per point; 0 = none) */
+int64_t geoa3_geo_scratch_bytes(int B, int N, int k);
 
 /* ------------------------------------------------------------------------------------------
  * Victim model: PointNet eval forward and input-gradient (Model/PointNet.py:56-160).

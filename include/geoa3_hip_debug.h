@@ -10,6 +10,7 @@
 #define GEOA3_HIP_DEBUG_H
 
 #include <stdint.h>
+#include "geoa3_hip.h" /* geoa3_geo_args */
 
 #ifdef __cplusplus
 extern "C" {
@@ -108,6 +109,24 @@ int geoa3_debug_grid_nn1_pair(const float* a, const float* r, int B, int Na, int
 #define GEOA3_KNN_ROUTE_SLABP32 5    /* slab_bin_kernel + knn_slabp_kernel<32, false> / <56, true>: position lists */
 #define GEOA3_KNN_ROUTE_SLABP56 6
 int geoa3_debug_knn_self_route(int B, int N, int K, int method, int has_prior, int scratch_ok);
+
+/* The kernel geoa3_geo_loss_grad (geoa3_hip.h) would run for these arguments: one of GEOA3_GEO_ROUTE_*, or GEOA3_EINVAL where
+ * the call is refused as malformed.  Only the sizes, the flags and WHICH pointers are given are looked at: no GPU work, no
+ * pointer is followed (tests/test_geo_route.py). */
+#define GEOA3_GEO_ROUTE_FUSED 0     /* geo_fused_kernel: N <= 1024, reverse-list rows in LDS */
+#define GEOA3_GEO_ROUTE_BIG 1       /* geo_big_kernel: N <= 4096 with scratch, fixed-point sums */
+#define GEOA3_GEO_ROUTE_LISTS 2     /* geo_loss_grad_kernel<true>: one workgroup, chunked reverse lists */
+#define GEOA3_GEO_ROUTE_ATOMICS 3   /* geo_loss_grad_kernel<false>: one workgroup, LDS float atomics */
+#define GEOA3_GEO_ROUTE_WIDE 4      /* geo_wide_pair_kernel + geo_wide_sum_kernel: 5840 <= N <= 8192 with scratch */
+#define GEOA3_GEO_ROUTE_REFUSED 5   /* geoa3_geo_loss_grad returns GEOA3_ENOSUPPORT */
+int geoa3_debug_geo_route(const geoa3_geo_args* args);
+
+/* The two-pass kernels behind GEOA3_GEO_ROUTE_WIDE on a cloud of any size from 64 to 8192 points (tests hold them to
+ * geo_big_kernel bit for bit where both run).  ranges: owner ranges per instance, 1..16; 0 = the dispatcher's choice (the
+ * fewest that fit LDS).  The gradient does not depend on it.  GEOA3_ENOSUPPORT when that many ranges do not fit LDS.
+ * args->scratch: geoa3_debug_geo_wide_scratch_bytes(B, N) bytes (== geoa3_geo_scratch_bytes beyond 4096 points). */
+int64_t geoa3_debug_geo_wide_scratch_bytes(int B, int N);
+int geoa3_debug_geo_wide(const geoa3_geo_args* args, int ranges, void* stream);
 
 /* Names and byte offsets (address order) of the buffers geoa3_pointnet_forward / _backward keep in their workspace:
  * tools/iteration_replay_soak.py attributes a run-to-run difference to the kernel that wrote it.  Returns the number

@@ -24,8 +24,29 @@ def timeit(fn, iters, warmup=3):
     return e0.elapsed_time(e1) * 1e3 / iters  # us
 
 
+def geo_case(ops, B, N, k, iters, **route):
+    """The fused objective on B clouds of N points, k neighbours: us per launch and ns per (centre, neighbour) pair.
+    Clouds of 1025..4096 points take geo_big_kernel, 5840..8192 the two-pass kernels (route: wide_ranges = S forces them)."""
+    g = torch.Generator().manual_seed(N + k)
+    u = torch.randn(B, 3, N, generator=g)
+    ori = (u / u.norm(dim=1, keepdim=True)).cuda().contiguous()
+    nrm = ori.clone()
+    adv = (ori + 0.01 * torch.randn(B, 3, N, generator=g).cuda()).contiguous()
+    _, knn_ori = ops.knn_planar(ori, ori, k + 1)
+    kap = ops.kappa(ori, nrm, knn_ori)
+    d_ao, i_ao, d_oa, i_oa = ops.nn1_pair(adv, ori)
+    _, knn_adv = ops.knn_planar(adv, adv, k + 1, knn_ori)
+    out = {}
+    if "wide_ranges" not in route:
+        route["scratch"] = ops.geo_scratch(B, N, adv.device, k)
+    us = timeit(lambda: ops.geo_loss_grad(adv, ori, normal_ori=nrm, kappa_ori=kap, d_ao=d_ao, i_ao=i_ao, d_oa=d_oa, i_oa=i_oa,
+                                          knn_adv=knn_adv, k=k, w_dis=1.0, w_hd=0.1, w_curv=1.0, out=out, **route), iters)
+    return us, us * 1e3 / (B * N * k)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--geo-only", action="store_true", help="only the objective on large clouds (the last lines)")
     ap.add_argument("--B", type=int, default=250)
     ap.add_argument("--N", type=int, default=1024)
     ap.add_argument("--k", type=int, default=16)
@@ -33,6 +54,21 @@ def main():
     a = ap.parse_args()
     from geoa3_amd import ops
     B, N, k = a.B, a.N, a.k
+    if not a.geo_only:
+        kernels(ops, a, B, N, k)
+    # the objective beyond 1024 points: geo_big_kernel at 4096, the two-pass kernels at 8192 (the first and the last line
+    # hold the same number of pairs) and, for the cost of their S scans, forced onto the 4096-point case
+    res = {}
+    for name, (gB, gN, gk, route) in {"geo_wide_b64_n8192_k32": (64, 8192, 32, {}), "geo_wide_b250_n8192_k16": (250, 8192, 16, {}),
+                                      "geo_wide_s1_b128_n4096_k32": (128, 4096, 32, dict(wide_ranges=1)),
+                                      "geo_wide_s4_b128_n4096_k32": (128, 4096, 32, dict(wide_ranges=4)),
+                                      "geo_big_b128_n4096_k32": (128, 4096, 32, {})}.items():
+        us, ns = geo_case(ops, gB, gN, gk, a.iters, **route)
+        res[name + "_us"], res[name + "_ns_per_pair"] = us, ns
+    print(json.dumps({kk: round(v, 4) for kk, v in res.items()}))
+
+
+def kernels(ops, a, B, N, k):
     g = torch.Generator().manual_seed(0)
     u = torch.randn(B, 3, N, generator=g)
     ori = (u / u.norm(dim=1, keepdim=True)).cuda().contiguous()
