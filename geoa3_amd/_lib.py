@@ -75,6 +75,10 @@ SIGNATURES = {
     "geoa3_knn": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "geoa3_knn_self_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "geoa3_knn_self": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
+    "geoa3_knn_gather": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_knn_scatter_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "geoa3_knn_gather_grad": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_knn_points_grad": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "geoa3_kappa": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_geo_loss_grad": (C.c_int, [C.POINTER(GeoArgs), vp]),
     "geoa3_geo_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
@@ -176,7 +180,7 @@ _lib = None
 
 ENOSUPPORT = -3   # GEOA3_ENOSUPPORT
 PN2_CONTRACT = 1   # GEOA3_PN2_CONTRACT
-ABI_VERSION = 606  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
+ABI_VERSION = 607  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
 
 
 class Geoa3Error(RuntimeError):

@@ -10,6 +10,8 @@ differentiates through it, a registered autograd formula.  `geoa3_amd.ops.knn_po
     geoa3::nn1_pair        knn_points(K=1) both directions            Lib/loss_utils.py:32-33,41,48,70,92
     geoa3::knn             knn_points(K)                              Lib/loss_utils.py:57,77
     geoa3::knn_points      the pytorch3d operator itself ([b,n,3] arguments, int64 idx, differentiable dists)
+    geoa3::knn_points_grad its backward, every point's terms in a fixed order      (pytorch3d knn backward)
+    geoa3::knn_gather / _grad   pytorch3d.ops.knn_gather and its ordered backward  Lib/loss_utils.py:58,71,78
     geoa3::kappa           _get_kappa_ori / the forward of _get_kappa_adv   Lib/loss_utils.py:52-82
     geoa3::geo_loss_grad   CD / HD / L2 / curvature values and d constrain / d adv   Attacker/geoA3_attack.py:131-166
     geoa3::point_loss      chamfer / pseudo-chamfer / hausdorff / l2 with autograd    Lib/loss_utils.py:25-50
@@ -125,17 +127,77 @@ def _knn_points_setup(ctx, inputs, output):
 
 
 def _knn_points_backward(ctx, gd, _gi):
-    # pytorch3d's knn backward: dp1 += 2 g (p1 - p2[idx]);  dp2[idx] -= the same (scatter-add)
+    # pytorch3d's knn backward: dp1 += 2 g (p1 - p2[idx]);  dp2[idx] -= the same, every point's terms in a fixed order
     p1, p2, idx = ctx.saved_tensors
-    b, n1, K = idx.shape
-    nb = ops.knn_gather(p2, idx)                         # [b,n1,K,3]
-    diff = 2.0 * gd.unsqueeze(-1) * (p1.unsqueeze(2) - nb)
-    g1 = diff.sum(2)
-    g2 = torch.zeros_like(p2).scatter_add(1, idx.reshape(b, n1 * K, 1).expand(b, n1 * K, 3), -diff.reshape(b, n1 * K, 3))
+    g1, g2 = torch.ops.geoa3.knn_points_grad(p1, p2, idx, gd)
     return g1, g2, None
 
 
 knn_points_op.register_autograd(_knn_points_backward, setup_context=_knn_points_setup)
+
+def _no_second_derivative(name):
+    def backward(ctx, *grads):
+        raise RuntimeError("geoa3::%s is a first derivative and has no derivative of its own: nothing in the package or the "
+                           "reference differentiates twice through knn_points / knn_gather (create_graph=True)" % name)
+    return backward
+
+
+@custom_op("geoa3::knn_points_grad", mutates_args=(), device_types="cuda")
+def knn_points_grad(p1: Tensor, p2: Tensor, idx: Tensor, gd: Tensor) -> Tuple[Tensor, Tensor]:
+    """The backward of geoa3::knn_points through dists: p1 [b,n1,3], p2 [b,n2,3], idx int64 / gd [b,n1,K] ->
+    (d p1 [b,n1,3], d p2 [b,n2,3]), each point's terms added in ascending (query, neighbour) order."""
+    g1, g2 = ops.knn_points_grad(p1.detach().contiguous().float(), p2.detach().contiguous().float(),
+                                 idx.contiguous().long(), gd.detach().contiguous().float())
+    return g1.to(p1.dtype), g2.to(p2.dtype)
+
+
+@knn_points_grad.register_fake
+def _(p1, p2, idx, gd):
+    return p1.new_empty(p1.shape), p2.new_empty(p2.shape)
+
+
+knn_points_grad.register_autograd(_no_second_derivative("knn_points_grad"))
+
+
+# ------------------------------------------------------------------------------------------------ pytorch3d.ops.knn_gather
+@custom_op("geoa3::knn_gather", mutates_args=(), device_types="cuda")
+def knn_gather_op(x: Tensor, idx: Tensor) -> Tensor:
+    """x [b,m,u] float32, idx int64 [b,l,k] -> [b,l,k,u]."""
+    return ops.knn_gather_fwd(x.detach().contiguous(), idx.contiguous())
+
+
+@knn_gather_op.register_fake
+def _(x, idx):
+    return x.new_empty(idx.shape[0], idx.shape[1], idx.shape[2], x.shape[2], dtype=_f32)
+
+
+@custom_op("geoa3::knn_gather_grad", mutates_args=(), device_types="cuda")
+def knn_gather_grad(g: Tensor, idx: Tensor, m: int) -> Tensor:
+    """The backward of geoa3::knn_gather: g [b,l,k,u], idx int64 [b,l,k] -> d x [b,m,u], row j the sum of the g[b,l,k,:]
+    with idx[b,l,k] == j in ascending (l, k) order."""
+    return ops.knn_gather_grad(g.detach().contiguous().float(), idx.contiguous(), int(m))
+
+
+@knn_gather_grad.register_fake
+def _(g, idx, m):
+    return g.new_empty(g.shape[0], m, g.shape[3], dtype=_f32)
+
+
+knn_gather_grad.register_autograd(_no_second_derivative("knn_gather_grad"))
+
+
+def _knn_gather_setup(ctx, inputs, output):
+    x, idx = inputs
+    ctx.save_for_backward(idx)
+    ctx.m = x.shape[1]
+
+
+def _knn_gather_backward(ctx, g):
+    (idx,) = ctx.saved_tensors
+    return torch.ops.geoa3.knn_gather_grad(g, idx, ctx.m), None
+
+
+knn_gather_op.register_autograd(_knn_gather_backward, setup_context=_knn_gather_setup)
 
 # ------------------------------------------------------------------------------------------------ Lib/loss_utils.py
 _KINDS = {"cd": 0, "pcd": 1, "hd": 2, "l2": 3}

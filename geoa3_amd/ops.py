@@ -373,15 +373,95 @@ def reg_fold(loss: Optional[Tensor], grad: Optional[Tensor], w: float, B: int, N
 _KNN = collections.namedtuple("KNN", ["dists", "idx", "knn"])
 
 
-def knn_points(p1: Tensor, p2: Tensor, K: int = 1, **_ignored):
-    """pytorch3d.ops.knn_points(p1 [b,n1,3], p2 [b,n2,3], K) -> KNN(dists, idx, knn=None)."""
+def _check_lengths(name: str, lengths, b: int, n: int) -> None:
+    """Ragged batches are not supported: a `lengths` argument must say that every cloud is full."""
+    if lengths is None:
+        return
+    t = torch.as_tensor(lengths)
+    if t.numel() != b or not bool((t.reshape(-1) == n).all()):
+        raise _lib.Geoa3Error("knn_points: %s must be None or %d for each of the %d clouds (ragged batches are not "
+                              "supported)" % (name, n, b))
+
+
+def knn_points(p1: Tensor, p2: Tensor, K: int = 1, return_nn: bool = False, lengths1=None, lengths2=None, **_ignored):
+    """pytorch3d.ops.knn_points(p1 [b,n1,3], p2 [b,n2,3], K) -> KNN(dists, idx, knn).  The gradient through `dists` is
+    summed per point in ascending (query, neighbour) order (geoa3_knn_points_grad): the same bits on every run.
+    return_nn: knn = knn_gather(p2, idx) [b,n1,K,3], differentiable in p2 (None otherwise).  lengths1 / lengths2 other
+    than None or all-full raise Geoa3Error."""
     from . import library  # noqa: F401  (registers geoa3::knn_points with its autograd formula)
+    _check_lengths("lengths1", lengths1, p1.shape[0], p1.shape[1])
+    _check_lengths("lengths2", lengths2, p2.shape[0], p2.shape[1])
     d, idx = torch.ops.geoa3.knn_points(p1, p2, int(K))
-    return _KNN(d, idx, None)
+    knn = None
+    if return_nn:   # (the search has no CPU kernel: whatever got here is a device tensor, or a fake one of any device)
+        knn = torch.ops.geoa3.knn_gather(p2, idx) if p2.dtype == torch.float32 else knn_gather(p2, idx)
+    return _KNN(d, idx, knn)
 
 
 def knn_gather(x: Tensor, idx: Tensor) -> Tensor:
-    """pytorch3d.ops.knn_gather(x [b,m,u], idx [b,l,k]) -> [b,l,k,u] (pure data movement)."""
+    """pytorch3d.ops.knn_gather(x [b,m,u], idx [b,l,k]) -> [b,l,k,u] (pure data movement).  float32 device tensors: the
+    library's gather (geoa3::knn_gather), whose gradient sums every row of x in ascending (l, k) order; anything else:
+    torch.gather."""
+    if x.is_cuda and idx.is_cuda and x.dtype == torch.float32 and idx.dtype == torch.int64 and x.dim() == 3 and idx.dim() == 3:
+        from . import library  # noqa: F401
+        return torch.ops.geoa3.knn_gather(x, idx)
     b, m, u = x.shape
     _, l, k = idx.shape
     return torch.gather(x, 1, idx.reshape(b, l * k, 1).expand(b, l * k, u)).view(b, l, k, u)
+
+
+def knn_scatter_scratch(B: int, E: int, M: int, device) -> Tensor:
+    """Scratch of knn_gather_grad / knn_points_grad for B instances of E entries that point into M rows."""
+    nbytes = int(_lib.load().geoa3_knn_scatter_scratch_bytes(B, E, M))
+    if nbytes < 0:
+        raise _lib.Geoa3Error("knn scatter: sizes out of range (B=%d, entries=%d, rows=%d)" % (B, E, M))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def knn_gather_fwd(x: Tensor, idx: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """geoa3_knn_gather: x [B,M,U] float32, idx int64 [B,L,K] -> [B,L,K,U]; an index outside [0,M) gives NaN."""
+    B, M, U = x.shape
+    _, L, K = idx.shape
+    if out is None:
+        out = torch.empty(B, L, K, U, device=x.device, dtype=torch.float32)
+    if out.numel():
+        check(_lib.load().geoa3_knn_gather(_p(x, torch.float32), _p(idx, torch.int64), B, M, L, K, U, _p(out, torch.float32),
+                                           _stream()), "geoa3_knn_gather")
+    return out
+
+
+def knn_gather_grad(g: Tensor, idx: Tensor, M: int, scratch: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """geoa3_knn_gather_grad: g [B,L,K,U] float32, idx int64 [B,L,K] -> gx [B,M,U], row j the sequential float32 sum of
+    the g[b,l,k,:] with idx[b,l,k] == j in ascending l K + k (indices outside [0,M) dropped)."""
+    B, L, K, U = g.shape
+    if out is None:
+        out = torch.empty(B, M, U, device=g.device, dtype=torch.float32)
+    if g.numel() == 0:
+        return out.zero_()
+    if out.numel():
+        if scratch is None:
+            scratch = knn_scatter_scratch(B, L * K, M, g.device)
+        check(_lib.load().geoa3_knn_gather_grad(_p(g, torch.float32), _p(idx, torch.int64), B, M, L, K, U,
+                                                _p(out, torch.float32), _p(scratch), _stream()), "geoa3_knn_gather_grad")
+    return out
+
+
+def knn_points_grad(p1: Tensor, p2: Tensor, idx: Tensor, gd: Tensor, want1: bool = True, want2: bool = True,
+                    scratch: Optional[Tensor] = None, out=None):
+    """geoa3_knn_points_grad: p1 [B,N1,3], p2 [B,N2,3] float32, idx int64 / gd float32 [B,N1,K] -> (g1 [B,N1,3] | None,
+    g2 [B,N2,3] | None): pytorch3d's knn backward, every point's terms added in ascending (query, neighbour) order."""
+    B, N1, _ = p1.shape
+    N2 = p2.shape[1]
+    K = idx.shape[2]
+    g1, g2 = out if out is not None else (None, None)
+    if want1 and g1 is None:
+        g1 = torch.empty(B, N1, 3, device=p1.device, dtype=torch.float32)
+    if want2 and g2 is None:
+        g2 = torch.empty(B, N2, 3, device=p1.device, dtype=torch.float32)
+    if want2 and scratch is None:
+        scratch = knn_scatter_scratch(B, N1 * K, N2, p1.device)
+    check(_lib.load().geoa3_knn_points_grad(_p(p1, torch.float32), _p(p2, torch.float32), _p(idx, torch.int64),
+                                            _p(gd, torch.float32), B, N1, N2, K, _p(g1, torch.float32) if want1 else None,
+                                            _p(g2, torch.float32) if want2 else None, _p(scratch) if want2 else None,
+                                            _stream()), "geoa3_knn_points_grad")
+    return (g1 if want1 else None), (g2 if want2 else None)

@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 606
+#define GEOA3_ABI_VERSION 607
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -96,6 +96,35 @@ int geoa3_knn(const float* q, const float* r, int B, int Nq, int Nr, int K,
 int64_t geoa3_knn_self_scratch_bytes(int B, int N);
 int geoa3_knn_self(const float* pc, int B, int N, int K, const int32_t* prior, float* dists, int32_t* idx,
                    void* scratch, int method, void* stream);
+
+/* pytorch3d.ops.knn_gather and the backward passes of knn_gather / knn_points, in the OPERATORS' layouts -- NOT the planar
+ * one of the rest of this header: point-major float32 (x [B,M,U], p [B,N,3]) and int64 indices, as the operators hand them
+ * over; no conversion pass.  Sizes: K >= 1, U >= 1, E = L K entries per instance with B E < 2^31 and B (M + 1) < 2^31
+ * (GEOA3_EINVAL / GEOA3_ENOSUPPORT otherwise).  Every output element is written.  An index outside [0, M) is the caller's
+ * error: it is never dereferenced -- the gather writes NaN to that element, the backward passes drop the term.
+ * Where pytorch3d (and torch.scatter_add) sum with float atomics, every sum here is SEQUENTIAL in float32, starts from
+ * +0.0f and runs in ascending entry number e = l K + k: a function of the call's arguments only (not of the run, of the
+ * other instances of the batch or of workgroup ids), which a float32 loop on the CPU reproduces bit for bit.
+ *
+ * knn_gather (Lib/loss_utils.py:58,71,78, Attacker/geoA3_attack.py:66,81, Lib/utility.py:46,97,121):
+ *   out[b,l,k,:] = x[b, idx[b,l,k], :];  x [B,M,U], idx [B,L,K], out [B,L,K,U]. */
+int geoa3_knn_gather(const float* x, const int64_t* idx, int B, int M, int L, int K, int U, float* out, void* stream);
+/* scratch of the two backward passes (the counting sort of an instance's E entries by destination): bytes, < 0 when the
+ * sizes are out of range; contents irrelevant, 4-byte aligned. */
+int64_t geoa3_knn_scatter_scratch_bytes(int B, int E, int M);
+/* the backward of the gather at the same call sites: gx[b,j,c] = sum of g[b,l,k,c] over the entries with idx[b,l,k] == j
+ * (+0.0 where nobody points);  g [B,L,K,U], gx [B,M,U], scratch: geoa3_knn_scatter_scratch_bytes(B, L K, M). */
+int geoa3_knn_gather_grad(const float* g, const int64_t* idx, int B, int M, int L, int K, int U, float* gx, void* scratch,
+                          void* stream);
+/* the backward of knn_points through `dists` (pytorch3d's knn backward; the searches of Lib/loss_utils.py:57,70,77 and
+ * Attacker/geoA3_attack.py:65,80 whose distances are differentiated):
+ *   t(i,k,c) = fl( fl(2 gd[i,k]) * fl(p1[i,c] - p2[idx[i,k],c]) )        (no fused multiply-add)
+ *   g1[i,c]  = sum over ascending k of t(i,k,c)
+ *   g2[j,c]  = sum of -t(i,k,c) over the entries with idx[i,k] == j, in ascending e = i K + k
+ * p1 [B,N1,3], p2 [B,N2,3], idx / gd [B,N1,K]; g1 [B,N1,3] or NULL, g2 [B,N2,3] or NULL (not both);
+ * scratch: geoa3_knn_scatter_scratch_bytes(B, N1 K, N2), may be NULL when g2 is. */
+int geoa3_knn_points_grad(const float* p1, const float* p2, const int64_t* idx, const float* gd, int B, int N1, int N2, int K,
+                          float* g1, float* g2, void* scratch, void* stream);
 
 
 /* _get_kappa_ori (Lib/loss_utils.py:52-62) given the self K-NN table knn_idx [B,N,k+1]
