@@ -18,7 +18,9 @@
 //     [32 s + 8 (lane >> 4) + j]) (geoa3_amd/pointnet.py pack_wide_split16), 64 bytes per lane and k-step, through a
 //     two-step register ring that runs across the channel groups.
 // The A fragments are double-buffered by HALF k-steps (four point tiles): the half just consumed is refilled for the next
-// k-step while the other half's 24 MFMAs run.
+// k-step while the other half's 24 MFMAs run.  The first MFMA of each accumulator takes a literal zero C operand (+0, what
+// the 64 v_mov per channel group wrote before); the group's first PF k-steps are a copy of the loop body for that (conv5
+// alone 417.4 -> 413.4 us, same bits: profiles/tnet_conv3_ab.txt).
 //
 // A work unit is (instance, 128-point tile, all 8 groups of 128 channels), as in the T-Net kernel: a tile is read, scaled,
 // split and written to LDS once.  (Until the unit was widened a tile's two channel halves were separate units and each
@@ -36,6 +38,7 @@
 #include "pointnet_kernels.h"
 #include "profile.h"
 #include "wide_epilogue.h"
+#include <type_traits>
 
 namespace {
 
@@ -214,14 +217,9 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
         Wn[c2] = wbase(g + 1 < g_end ? g + 1 : g, c2);
       }
       f32x4 acc[8][2];
-#pragma unroll
-      for (int t = 0; t < 8; ++t)
-#pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc[t][c2][i] = 0.f;
-#pragma unroll 1
-      for (int s0 = 0; s0 < KS; s0 += PF) {
+      // PF k-steps from s0 on; FIRST: the group's first ones, whose first k-step starts from a zero C operand
+      auto ksteps = [&](int s0, auto first_tag) {
+        constexpr bool FIRST = decltype(first_tag)::value;
 #pragma unroll
         for (int f = 0; f < PF; ++f) {
           const int s = s0 + f;
@@ -243,7 +241,9 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
             for (int t = 0; t < 4; ++t)
 #pragma unroll
               for (int c2 = 0; c2 < 2; ++c2) {
-                acc[4 * hf + t][c2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[hf][t], wh[c2], acc[4 * hf + t][c2], 0, 0, 0);
+                f32x4 c0 = acc[4 * hf + t][c2];
+                if (FIRST && f == 0) c0 = f32x4{0.f, 0.f, 0.f, 0.f};
+                acc[4 * hf + t][c2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[hf][t], wh[c2], c0, 0, 0, 0);
                 acc[4 * hf + t][c2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[hf][t], wl[c2], acc[4 * hf + t][c2], 0, 0, 0);
                 acc[4 * hf + t][c2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[hf][t], wh[c2], acc[4 * hf + t][c2], 0, 0, 0);
               }
@@ -253,7 +253,10 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
             for (int t = 0; t < 4; ++t) a_rd(sn, 4 * hf + t, Ah[hf][t], Al[hf][t]);
           }
         }
-      }
+      };
+      ksteps(0, std::true_type{});
+#pragma unroll 1
+      for (int s0 = PF; s0 < KS; s0 += PF) ksteps(s0, std::false_type{});
       // lane: channel co0 + 16 c2 + p16; acc[t][c2][r]: point n0 + 16 t + 4 q4 + r.  Ascending point order, strict >
       const bool full = n0 + W16_PTS <= N;
       if (GEOA3_W16_CUT & 2) {   // the accumulators stay live, nothing is reduced or published

@@ -28,9 +28,26 @@
 // those of the fp32 path; the epilogue is the two-pass, branch-free first maximum of wide_epilogue.h (the lane's maximum
 // over its 64 values, then the lowest point that equals it; ragged tiles masked to -inf first): the layer alone 188.0 ->
 // 183.4 us against the one-pass compare / select chain, same bits (NOTEBOOK 10).
+//
+// The k loop's operand pipeline (NOTEBOOK 10, "T-Net conv3 dissected"; profiles/tnet_conv3_ab.txt):
+//   A: the fragments of one whole k-step live in registers (4 point tiles x hi / lo = 8 x half8).  A tile's pair is refilled
+//      for the NEXT k-step right behind the tile's own three MFMAs, so a read has the other three tiles' 9 MFMAs (~290
+//      cycles) of cover -- the finest form of conv5's half-k-step refill, +16 registers (212 of 256, no scratch).  The
+//      fragments do not depend on the channel group: the last k-step of a group reads k-step 0 again and the next group
+//      starts with its operands present.  After a unit's last group that read is dead; the epilogue's LDS traffic and the
+//      __syncthreads() in front of the next staging pass wait for it (lgkmcnt(0)) before any wave overwrites the image.
+//   B: ring slot f is reloaded for k-step s + PF behind the 12 MFMAs that read it (36 MFMAs ahead of its next use, no copy).
+//   `sched_barrier(0)` holds both in place.  Left to itself the scheduler sank every load to its use: each ds_read_b128
+//   directly in front of its MFMA behind an lgkmcnt(0), and the ring's global loads to the end of the block with a
+//   vmcnt wait and a register copy behind them -- the matrix pipe idle for an LDS or an L2 round trip every few MFMAs
+//   whenever the CU's other workgroup was staging or in an epilogue.
+//   C: the first MFMA of each accumulator takes a literal zero C operand (+0, what the 64 v_mov per group wrote before);
+//   the first block of PF k-steps is a copy of the block's code for that, so a group's 96 MFMAs are straight-line code.
+// The MFMAs on each accumulator are the same, in the same order (hh, hl, lh per k-step, k ascending): same bits.
 #include "pointnet_kernels.h"
 #include "profile.h"
 #include "wide_epilogue.h"
+#include <type_traits>
 
 namespace {
 
@@ -41,8 +58,9 @@ constexpr int SP_ROWB = 272;                 // bytes per LDS row: 128 fp16 + 16
 constexpr int SP_PIECEB = SP_PTS * SP_ROWB;  // 34,816
 constexpr int SP_LDS = 2 * SP_PIECEB;        // 69,632 B: two workgroups per CU
 
-// Timing-only variant builds (tools/build_w16_variants.sh, never the shipped library), the bit of pointnet_wide16.hip's
-// GEOA3_W16_CUT: 2 = no epilogue / keys
+// Timing-only variant builds (tools/build_w16_variants.sh, never the shipped library): the bit mask of pointnet_wide16.hip's
+// GEOA3_W16_CUT.  1 = no staging (the LDS image is left as it is, the barriers stay), 2 = no epilogue / keys, 4 = no
+// weight-fragment loads (the ring is reused).  A cut build computes wrong values; it touches no byte the shipped kernel does not.
 #ifndef GEOA3_WSP_CUT
 #define GEOA3_WSP_CUT 0
 #endif
@@ -104,65 +122,75 @@ __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs
     // ---- stage: every value of the tile goes through registers once: maximum -> scale -> split -> LDS.
     // Wave w takes the channel octets w, w+4, ..; a lane one point per pass (rows 0..127 of the image = points
     // n0 .. n0+127): 8 coalesced row reads per octet.
-    float xv[2][4][8];
-    {
-      int ldx = a.ldX;
-      asm volatile("" : "+s"(ldx));              // opaque: keeps the row offsets from being hoisted out of the unit
-                                                 // loop (they were spilled to scratch)
+    float unscale = a.unscale;
+    if (GEOA3_WSP_CUT & 1) {   // the barriers of the staging pass, none of its loads, arithmetic or LDS writes
+      stamp();
+      flush();
+      __syncthreads();
+      __syncthreads();
+      __syncthreads();
+    } else {
+      float xv[2][4][8];
+      {
+        int ldx = a.ldX;
+        asm volatile("" : "+s"(ldx));              // opaque: keeps the row offsets from being hoisted out of the unit
+                                                   // loop (they were spilled to scratch)
 #pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int n = n0 + pass * 64 + lane;
-        const bool in = n < N;
-        const float* px = X + (in ? n : 0);
+        for (int pass = 0; pass < 2; ++pass) {
+          const int n = n0 + pass * 64 + lane;
+          const bool in = n < N;
+          const float* px = X + (in ? n : 0);
+#pragma unroll
+          for (int oc = 0; oc < 4; ++oc)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              const float v = px[(size_t)(((wave + 4 * oc) * 8 + i) * ldx)];
+              xv[pass][oc][i] = in ? v : 0.f;
+            }
+        }
+      }
+      float m = 0.f;
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass)
 #pragma unroll
         for (int oc = 0; oc < 4; ++oc)
 #pragma unroll
+          for (int i = 0; i < 8; ++i) m = fmaxf(m, __builtin_fabsf(xv[pass][oc][i]));   // NaN is caught through xs below
+      m = wave_max(m);
+      stamp();
+      flush();           // the previous unit's maxima, behind this unit's loads
+      __syncthreads();   // every wave is done with the previous tile (LDS image and s_max)
+      if (lane == 0) s_max[wave] = m;
+      __syncthreads();
+      m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+      unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
+      bool bad = E == 255u;    // inf (a NaN does not survive fmaxf: caught below)
+      E = sf_clamp(E);
+      const float scale = sf_scale(E);
+      unscale = a.unscale * sf_unscale(E);
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass) {
+        const int p = pass * 64 + lane;
+#pragma unroll
+        for (int oc = 0; oc < 4; ++oc) {
+          half8 hi, lo;
+#pragma unroll
           for (int i = 0; i < 8; ++i) {
-            const float v = px[(size_t)(((wave + 4 * oc) * 8 + i) * ldx)];
-            xv[pass][oc][i] = in ? v : 0.f;
+            const float xs = xv[pass][oc][i] * scale;
+            bad |= xs != xs;
+            _Float16 h, l;
+            sf_split(xs, h, l);
+            hi[i] = h;
+            lo[i] = l;
           }
-      }
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass)
-#pragma unroll
-      for (int oc = 0; oc < 4; ++oc)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) m = fmaxf(m, __builtin_fabsf(xv[pass][oc][i]));   // NaN is caught through xs below
-    m = wave_max(m);
-    stamp();
-    flush();           // the previous unit's maxima, behind this unit's loads
-    __syncthreads();   // every wave is done with the previous tile (LDS image and s_max)
-    if (lane == 0) s_max[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
-    bool bad = E == 255u;    // inf (a NaN does not survive fmaxf: caught below)
-    E = sf_clamp(E);
-    const float scale = sf_scale(E), unscale = a.unscale * sf_unscale(E);
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      const int p = pass * 64 + lane;
-#pragma unroll
-      for (int oc = 0; oc < 4; ++oc) {
-        half8 hi, lo;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float xs = xv[pass][oc][i] * scale;
-          bad |= xs != xs;
-          _Float16 h, l;
-          sf_split(xs, h, l);
-          hi[i] = h;
-          lo[i] = l;
+          unsigned char* dst = smem_raw + p * SP_ROWB + (wave + 4 * oc) * 16;
+          *reinterpret_cast<half8*>(dst) = hi;
+          *reinterpret_cast<half8*>(dst + SP_PIECEB) = lo;
         }
-        unsigned char* dst = smem_raw + p * SP_ROWB + (wave + 4 * oc) * 16;
-        *reinterpret_cast<half8*>(dst) = hi;
-        *reinterpret_cast<half8*>(dst + SP_PIECEB) = lo;
       }
+      if (__syncthreads_or(bad))   // loud, not silently wrong: key ~0 decodes to NaN in wide_finalize_kernel
+        for (int c = tid; c < a.Co; c += SP_THREADS) atomicMax(a.keys + (size_t)b * a.Co + c, ~0ull);
     }
-    if (__syncthreads_or(bad))   // loud, not silently wrong: key ~0 decodes to NaN in wide_finalize_kernel
-      for (int c = tid; c < a.Co; c += SP_THREADS) atomicMax(a.keys + (size_t)b * a.Co + c, ~0ull);
     stamp();
     // A operand of lane (r = l31, h = kh), tile t, k-step s (ci0 = 16 s): row 32t + r, bytes (ci0 + 8h) * 2
     const unsigned char* abase = smem_raw + l31 * SP_ROWB + kh * 16;
@@ -181,6 +209,16 @@ __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs
         wf[f][c][1] = W0[(size_t)(2 * f + 1) * 64];
       }
     }
+    // A fragments of k-step f of the block at `base` (ci0 = 16 (PF sb + f)), point tile t
+    auto a_rd = [&](const unsigned char* base, int f, int t, half8& h, half8& l) {
+      const unsigned char* ap = base + 32 * t * SP_ROWB + f * 32;
+      h = *reinterpret_cast<const half8*>(ap);
+      l = *reinterpret_cast<const half8*>(ap + SP_PIECEB);
+    };
+    // k-step 0 of the unit's first group; every later k-step, and k-step 0 of the following groups, is read under MFMAs
+    half8 Ah[4], Al[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) a_rd(abase, 0, t, Ah[t], Al[t]);
 #pragma unroll 1
     for (int g = g_begin; g < g_end; ++g) {
       const half8 *Wp[CB], *Wn[CB];
@@ -190,58 +228,49 @@ __global__ __launch_bounds__(SP_THREADS, SP_OCC) void wide_split_kernel(WideArgs
         Wn[c] = wbase(g + 1 < g_end ? g + 1 : g, c);
       }
       f32x16 acc[CB][4];
-#pragma unroll
-      for (int c = 0; c < CB; ++c)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) acc[c][t][i] = 0.f;
-      auto lds_rd = [&](const unsigned char* base, int f, int t, half8& h, half8& l) {
-        const unsigned char* ap = base + 32 * t * SP_ROWB + f * 32;
-        h = *reinterpret_cast<const half8*>(ap);
-        l = *reinterpret_cast<const half8*>(ap + SP_PIECEB);
-      };
-      // software pipeline over (k-step, tile): the A fragments of the next tile-step are read from LDS while the
-      // MFMAs of the current one run
-      // tile-step j = 4 f + t of the current block (j >= 4 PF: the next block's first step)
-      auto rd_step = [&](const unsigned char* ap0, const unsigned char* ap1, int j, half8& h, half8& l) {
-        if (j < 4 * PF) lds_rd(ap0, j >> 2, j & 3, h, l);
-        else lds_rd(ap1, (j - 4 * PF) >> 2, (j - 4 * PF) & 3, h, l);
-      };
-      half8 qh[2], ql[2];
-      rd_step(abase, abase, 0, qh[0], ql[0]);
-#pragma unroll 1
-      for (int sb = 0; sb < NBLK; ++sb) {
-        // k-steps PF sb .. PF sb + PF - 1: ci0 = 16 PF sb + 16 f
+      // one block of PF k-steps (PF sb .. PF sb + PF - 1: ci0 = 16 PF sb + 16 f); FIRST: the group's first block, whose
+      // first k-step starts the accumulators from a zero C operand
+      auto kblock = [&](int sb, auto first_tag) {
+        constexpr bool FIRST = decltype(first_tag)::value;
         const unsigned char* ap0 = abase + sb * (PF * 32);
-        const int sn = sb + 1 < NBLK ? sb + 1 : sb;
-        const unsigned char* ap1 = abase + sn * (PF * 32);
+        const unsigned char* ap1 = abase + (sb + 1 < NBLK ? sb + 1 : 0) * (PF * 32);   // the last block wraps to k-step 0
 #pragma unroll
         for (int f = 0; f < PF; ++f) {
-          half8 wh[CB], wl[CB];
-#pragma unroll
-          for (int c = 0; c < CB; ++c) {
-            wh[c] = wf[f][c][0];
-            wl[c] = wf[f][c][1];
-            const half8* src = sb + 1 < NBLK ? Wp[c] + (size_t)(2 * PF * 64) * (sb + 1) : Wn[c];
-            wf[f][c][0] = src[(2 * f) * 64];
-            wf[f][c][1] = src[(2 * f + 1) * 64];
-          }
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
-            const int j = 4 * f + t;
-            rd_step(ap0, ap1, j + 1, qh[(j + 1) & 1], ql[(j + 1) & 1]);
-            const half8 xh = qh[j & 1], xl = ql[j & 1];
+            __builtin_amdgcn_sched_barrier(0);
             // operands swapped as in the fp32 kernel: rows = points, columns = channels
 #pragma unroll
             for (int c = 0; c < CB; ++c) {
-              acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wh[c], acc[c][t], 0, 0, 0);
-              acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wl[c], acc[c][t], 0, 0, 0);
-              acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, wh[c], acc[c][t], 0, 0, 0);
+              f32x16 c0 = acc[c][t];
+              if (FIRST && f == 0)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) c0[i] = 0.f;
+              acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[t], wf[f][c][0], c0, 0, 0, 0);
+              acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[t], wf[f][c][1], acc[c][t], 0, 0, 0);
+              acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[t], wf[f][c][0], acc[c][t], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // tile t is consumed: refill it for the next k-step while the other tiles' 9 MFMAs run
+            if (f + 1 < PF) a_rd(ap0, f + 1, t, Ah[t], Al[t]);
+            else a_rd(ap1, 0, t, Ah[t], Al[t]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          // ring slot f is consumed: refill it for k-step s + PF (36 MFMAs ahead)
+          if (!(GEOA3_WSP_CUT & 4)) {
+#pragma unroll
+            for (int c = 0; c < CB; ++c) {
+              const half8* src = sb + 1 < NBLK ? Wp[c] + (size_t)(2 * PF * 64) * (sb + 1) : Wn[c];
+              wf[f][c][0] = src[(2 * f) * 64];
+              wf[f][c][1] = src[(2 * f + 1) * 64];
             }
           }
         }
-      }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      kblock(0, std::true_type{});
+#pragma unroll 1
+      for (int sb = 1; sb < NBLK; ++sb) kblock(sb, std::false_type{});
       stamp();
       // lane: channel co0 + l31; acc[t][r]: point n0 + 32t + (r&3) + 8(r>>2) + 4kh.  Ascending point order, strict >
       const bool full = n0 + SP_PTS <= N;
