@@ -22,13 +22,15 @@
 // the 64 v_mov per channel group wrote before); the group's first PF k-steps are a copy of the loop body for that (conv5
 // alone 417.4 -> 413.4 us, same bits: profiles/tnet_conv3_ab.txt).
 //
-// A work unit is (instance, 128-point tile, all 8 groups of 128 channels), as in the T-Net kernel: a tile is read, scaled,
-// split and written to LDS once.  (Until the unit was widened a tile's two channel halves were separate units and each
-// staged the tile for itself: conv5 alone at B = 250, N = 1024 449.0 -> 428.9 us, same bits; NOTEBOOK 10, "conv5
-// dissected".)  The two workgroups of a CU still run half a unit (now four groups) apart.  The unit's 4 x 8 x 32 packed
-// maxima wait for their atomicMax in the padding bytes of the image's rows: a second 8 KB array beside the 74,880-byte
-// image would leave no room for two workgroups per CU.  The kernel sits at 256 registers and spills (14 VGPRs, 60 bytes
-// per lane), but every scratch access lies in the staging part of the unit loop, none inside the channel-group or k loops.
+// Unit schedule, staging pass, key hand-off and launcher are those of wide_unit.h, shared with the T-Net kernel: a tile
+// is read, scaled, split and written to LDS once per unit.  (Until the unit was widened a tile's two channel halves were
+// separate units and each staged the tile for itself: conv5 alone at B = 250, N = 1024 449.0 -> 428.9 us, same bits;
+// NOTEBOOK 10, "conv5 dissected".)  This file's own: the two halo rows, staged between the shared pieces (one value
+// per thread, part of the tile's maximum), and where the unit's 4 x 8 x 32 packed maxima wait for their atomicMax -- in
+// the padding bytes of the image's rows: a second 8 KB array beside the 74,880-byte image would leave no room for two
+// workgroups per CU.  The kernel sits at 256 registers and spills (4 VGPRs, 20 bytes per lane), but every scratch
+// access lies in the staging part of the unit loop, none inside the channel-group or k loops.  (Sharing the pieces,
+// whichever, cost the layer 1.5-2 us of 404 against the same statements in place, the group loop identical: NOTEBOOK 10.)
 //
 // Epilogue of a channel group (wide_epilogue.h): the lane's maximum first (v_max3_f32), then the lowest point whose
 // accumulator equals it (one compare + one select per value, no branch), then the shuffles across the four lanes of a
@@ -36,16 +38,14 @@
 // scan it replaces had compiled to an exec-mask region with a branch per value: conv5 alone 442.3 -> 419.8 us, same bits;
 // NOTEBOOK 10.  Running the next group's first k-step under the index scan was built as well and lost: NOTEBOOK 8 row 41.)
 #include "pointnet_kernels.h"
-#include "profile.h"
 #include "wide_epilogue.h"
+#include "wide_unit.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int W16_THREADS = 256;
 constexpr int W16_OCC = 2;                        // workgroups per CU
-constexpr int W16_PTS = 128;
-constexpr int W16_ROWS = W16_PTS + 2;
+constexpr int W16_ROWS = WIDE_PTS + 2;
 constexpr int W16_ROWB = 288;
 constexpr int W16_PIECEB = W16_ROWS * W16_ROWB;   // 37,440
 constexpr int W16_LDS = 2 * W16_PIECEB;           // 74,880 B: two workgroups per CU
@@ -56,52 +56,30 @@ constexpr int W16_LDS = 2 * W16_PIECEB;           // 74,880 B: two workgroups pe
 #define GEOA3_W16_CUT 0
 #endif
 
-__global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a, int slots_per_xcd) {
+__global__ __launch_bounds__(WIDE_THREADS, W16_OCC) void wide16_kernel(WideArgs a, int slots_per_xcd) {
   constexpr int TAPS = 3;
-  constexpr int GROUPS = 8;                  // channel groups of 128 per unit: all 1024 channels, one staging pass per tile
   constexpr int KS = TAPS * 4;               // k-steps of 32 per channel tile
   constexpr int PF = 2;                      // k-steps of weight fragments in flight
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ float s_max[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p16 = lane & 15, q4 = lane >> 4, l31 = lane & 31,
-            kh = lane >> 5;
-  // packed maxima of the current unit, published while the next unit is staged (pointnet_wide_split.hip).  They live in
-  // the 32 pad bytes of the image's rows (4 keys per row, 2 x 128 rows = the 4 x 8 x 32 keys of a unit): neither the
-  // staging writes nor the A reads touch bytes 256..287 of a row, and a second 8 KB array would not leave room for two
-  // workgroups per CU
-  auto key_slot = [&](int i, int l) {   // channel tile i (< GROUPS) of this wave, channel l (< 32)
-    const int k = (wave * GROUPS + i) * 32 + l;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p16 = lane & 15, q4 = lane >> 4;
+  // the unit's packed maxima (wide_flush) live in the 32 pad bytes of the image's rows (4 keys per row, 2 x 128 rows = the
+  // 4 x 8 x 32 keys of a unit): neither the staging writes nor the A reads touch bytes 256..287 of a row
+  auto key_slot = [&](int i, int l) {   // channel tile i (< WIDE_GROUPS) of this wave, channel l (< 32)
+    const int k = (wave * WIDE_GROUPS + i) * 32 + l;
     unsigned char* row = smem_raw + (k >> 9) * W16_PIECEB + ((k >> 2) & 127) * W16_ROWB;
     return reinterpret_cast<unsigned long long*>(row + 256 + (k & 3) * 8);
   };
-  const int N = a.N, tiles = (N + W16_PTS - 1) / W16_PTS;
-  const int per_inst = tiles;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int inst_x = (a.B - xcd + 7) / 8;
-  const int units = inst_x * per_inst;
+  const int N = a.N;
   const half8* Wall = reinterpret_cast<const half8*>(a.Wh);
-  // see pointnet_wide_split.hip: the two workgroups of a CU run half a unit apart
-  if (tid == 0) s_max[0] = __int_as_float(__builtin_amdgcn_s_getreg((3 << 11) | 4) & 1);
-  __syncthreads();
-  bool late = __float_as_int(s_max[0]) != 0;
-  const int nmine = units > slot ? (units - slot + slots_per_xcd - 1) / slots_per_xcd : 0;
-  late = late && nmine > 0;
-  int pend_b = -1, pend_co = 0, pend_n = 0;
-  auto flush = [&]() {
-    if (pend_b < 0) return;
-    for (int i = kh; i < pend_n; i += 2)
-      atomicMax(a.keys + (size_t)pend_b * a.Co + pend_co + i * 128 + l31, *key_slot(i, l31));
-    pend_b = -1;
-  };
-  for (int it = 0; it < nmine + (late ? 1 : 0); ++it) {
-    const int u = slot + (it == nmine ? 0 : it) * slots_per_xcd;
-    const int g_begin = late && it == nmine ? GROUPS / 2 : 0;
-    const int g_end = late && it == 0 ? GROUPS / 2 : GROUPS;
-    const int qi = u / per_inst, r = u - qi * per_inst;
-    const int b = xcd + 8 * qi, tile = r;
-    const int n0 = tile * W16_PTS;
+  const WideSchedule sch = wide_schedule(a, slots_per_xcd, s_max);
+  WidePending pend;
+  auto flush = [&]() { wide_flush(pend, a, lane, key_slot); };
+  for (int it = 0; it < sch.iterations(); ++it) {
+    const WideUnit un = wide_unit(sch, it);
+    const int b = un.b, n0 = un.n0, g_begin = un.g_begin, g_end = un.g_end;
     const float* X = a.X + (size_t)b * a.sXb;
-    // ---- stage (as in the 32x32 kernel): maximum -> scale -> split -> LDS, rows 1..128 = points n0 .. n0 + 127;
+    // ---- stage (wide_unit.h): rows 1..128 of the image = points n0 .. n0 + 127;
     // the two halo rows (points n0 - 1, n0 + 128): one value per thread
     float unscale = a.unscale;
     if (GEOA3_W16_CUT & 1) {
@@ -111,61 +89,17 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
       float xv[2][4][8], xhalo = 0.f;
       {
         int ldx = a.ldX;
-        asm volatile("" : "+s"(ldx));
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-          const int n = n0 + pass * 64 + lane;
-          const bool in = n < N;
-          const float* px = X + (in ? n : 0);
-#pragma unroll
-          for (int oc = 0; oc < 4; ++oc)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-              const float v = px[(size_t)(((wave + 4 * oc) * 8 + i) * ldx)];
-              xv[pass][oc][i] = in ? v : 0.f;
-            }
-        }
-        const int nh = tid < 128 ? n0 - 1 : n0 + W16_PTS;
+        asm volatile("" : "+s"(ldx));   // opaque: see wide_load_tile
+        wide_load_tile(X, ldx, n0, N, lane, wave, xv);
+        const int nh = tid < 128 ? n0 - 1 : n0 + WIDE_PTS;
         if (nh >= 0 && nh < N) xhalo = X[(size_t)((tid & 127) * ldx) + nh];
       }
-      float m = __builtin_fabsf(xhalo);
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass)
-#pragma unroll
-        for (int oc = 0; oc < 4; ++oc)
-#pragma unroll
-          for (int i = 0; i < 8; ++i) m = fmaxf(m, __builtin_fabsf(xv[pass][oc][i]));
-      m = wave_max(m);
+      const float m = wide_abs_max(xv, __builtin_fabsf(xhalo));
       flush();
-      __syncthreads();
-      if (lane == 0) s_max[wave] = m;
-      __syncthreads();
-      m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-      unsigned E = (__float_as_uint(m) >> 23) & 0xffu;
-      bool bad = E == 255u;
-      E = sf_clamp(E);
-      const float scale = sf_scale(E);
-      unscale = a.unscale * sf_unscale(E);
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int p = 1 + pass * 64 + lane;
-#pragma unroll
-        for (int oc = 0; oc < 4; ++oc) {
-          half8 hi, lo;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const float xs = xv[pass][oc][i] * scale;
-            bad |= xs != xs;
-            _Float16 h, l;
-            sf_split(xs, h, l);
-            hi[i] = h;
-            lo[i] = l;
-          }
-          unsigned char* dst = smem_raw + p * W16_ROWB + (wave + 4 * oc) * 16;
-          *reinterpret_cast<half8*>(dst) = hi;
-          *reinterpret_cast<half8*>(dst + W16_PIECEB) = lo;
-        }
-      }
+      float scale;
+      bool bad = wide_tile_scale(m, s_max, lane, wave, scale, unscale);
+      unscale *= a.unscale;
+      bad |= wide_split_store<W16_ROWB, W16_PIECEB>(xv, scale, smem_raw + W16_ROWB, lane, wave);
       {
         const float xs = xhalo * scale;
         bad |= xs != xs;
@@ -175,8 +109,7 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
         *reinterpret_cast<_Float16*>(dst) = h;
         *reinterpret_cast<_Float16*>(dst + W16_PIECEB) = l;
       }
-      if (__syncthreads_or(bad))
-        for (int c = tid; c < a.Co; c += W16_THREADS) atomicMax(a.keys + (size_t)b * a.Co + c, ~0ull);
+      wide_poison(a, b, bad);
     }
     // A operand of lane (p16, q4), point tile t, k-step s (tap = s / 4, ci0 = 32 (s % 4)):
     //   row 16 t + p16 + tap, bytes (ci0 + 8 q4) * 2
@@ -258,7 +191,7 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
 #pragma unroll 1
       for (int s0 = PF; s0 < KS; s0 += PF) ksteps(s0, std::false_type{});
       // lane: channel co0 + 16 c2 + p16; acc[t][c2][r]: point n0 + 16 t + 4 q4 + r.  Ascending point order, strict >
-      const bool full = n0 + W16_PTS <= N;
+      const bool full = n0 + WIDE_PTS <= N;
       if (GEOA3_W16_CUT & 2) {   // the accumulators stay live, nothing is reduced or published
 #pragma unroll
         for (int t = 0; t < 8; ++t)
@@ -294,9 +227,9 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
       }
     }
     if (GEOA3_W16_CUT & 2) continue;
-    pend_b = b;
-    pend_co = g_begin * 128 + wave * 32;
-    pend_n = g_end - g_begin;
+    pend.b = b;
+    pend.co = g_begin * 128 + wave * 32;
+    pend.n = g_end - g_begin;
   }
   flush();
 }
@@ -304,16 +237,5 @@ __global__ __launch_bounds__(W16_THREADS, W16_OCC) void wide16_kernel(WideArgs a
 }  // namespace
 
 int launch_wide_max_split16(const WideArgs& a, hipStream_t s) {
-  if (a.Co != 1024 || a.taps != 3 || !a.keys || !a.Wh) return GEOA3_ENOSUPPORT;
-  geoa3_prof_begin(GEOA3_PROF_CONV5, s);
-  if (!a.keys_clean &&
-      hipMemsetAsync(a.keys, 0, (size_t)a.B * a.Co * sizeof(unsigned long long), s) != hipSuccess)
-    return GEOA3_ELAUNCH;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wide16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W16_LDS);
-  constexpr int SLOTS = 32 * W16_OCC;
-  hipLaunchKernelGGL(wide16_kernel, dim3(SLOTS * 8), dim3(W16_THREADS), W16_LDS, s, a, SLOTS);
-  launch_wide_finalize(a, s);
-  geoa3_prof_end(GEOA3_PROF_CONV5, s);
-  GEOA3_CHECK_LAUNCH();
-  return GEOA3_OK;
+  return wide_launch(wide16_kernel, W16_LDS, W16_OCC, 3, GEOA3_PROF_CONV5, a, s);
 }
