@@ -12,39 +12,21 @@
 // Here EVERY sum is sequential in float32, starts from +0.0f and runs in ascending entry number e = l K + k (g1: ascending
 // k), so a plain float32 loop on the CPU reproduces every element bit for bit, whatever the batch an instance is part of.
 //
-// The scatter is the scheme of three_interpolate_grad (pointnet2_interp.hip), restated for int64 indices, any segment
-// length and flat launches (no limit on B from the grid's y dimension).  The E = L K entries of an instance are sorted by
-// destination -- a counting sort into the caller's scratch -- then one thread per (destination, group of components)
-// walks its list:
-//   scratch (int32): start [B][M+1] | cursor [B][M] | bucket [B][E] | order [B][E]
-//   1. kso_count:  start[b][j] = number of entries that point at j (integer atomics: a count has no order)
-//   2. kso_scan:   start <- its exclusive prefix sum (one workgroup per instance), cursor <- start
-//   3. kso_place:  every entry takes the next free place of its destination's segment of `bucket` (integer atomic cursor:
-//                  the ORDER inside a segment depends on timing ...)
-//   4. kso_sort:   ... so every segment is sorted by e into `order` (the entries are distinct: the result is unique) by
-//                  rank counting -- the rank of an entry is the number of smaller ones in its segment.  Up to 64 entries: one
-//                  wavefront, lane shuffles.  Longer (a hub can receive all E entries): the whole workgroup, the segment
-//                  passing through LDS in tiles of KSO_TILE entries while every thread counts for KSO_KPT entries of its
-//                  own; any length, quadratic in it.
-//   5. the sums (kgg_sum / kpg_g2) in list order; an empty list writes +0.0.  Every element is written.
-// Two forms of the same five steps, the same bits: when an instance's tables fit the LDS of one compute unit
-// (2 M + 2 E + E / 65 + 2 ints <= KSL_LDS_MAX bytes: every shape of the reference's objective, e.g. M = 1024, E = 1024 x 17)
-// ONE workgroup per instance keeps them there and does all five steps in one launch (ksl_*: LDS atomics place the entries,
-// `scratch` is not touched); larger instances take the five launches through `scratch` (kso_*).
+// The scatter: the E = L K entries of an instance are sorted by destination into lists (dest_lists.h: the scheme, its
+// invariants and both of its forms), then one thread per (destination, group of components) walks its list (kgg_sum /
+// kpg_g2; an empty list writes +0.0; every element is written).  When an instance's tables fit the LDS of one compute unit
+// (ksl_lds_bytes <= KSL_LDS_MAX: every shape of the reference's objective, e.g. M = 1024, E = 1024 x 17) ONE workgroup per
+// instance builds them there and sums in the same launch (*_lds_kernel; `scratch` is not touched); larger instances take the
+// lists from launch_dest_lists through `scratch`.  The same bits either way.
 // An index outside [0, M) is the caller's error: it is neither wrapped nor clamped nor dereferenced -- the gather writes NaN
 // to that element, the backward passes drop the term (the entry is in no list).
 // No float atomics; a NaN or inf term is added like any other value.
-#include <climits>
-#include "common.h"
+#include "dest_lists.h"
 
 namespace {
 
-constexpr int KSO_TILE = 1024;   // entries of a long segment per LDS tile
-constexpr int KSO_KPT = 4;       // entries a thread ranks per pass over a long segment (256 threads: 1024 per pass)
 constexpr int KGG_CG = 4;        // components per thread of kgg_sum
 constexpr int MAX_GRID_Y = 65535;
-
-__device__ __forceinline__ bool kso_valid(int64_t j, int M) { return (uint64_t)j < (uint64_t)M; }
 
 // ------------------------------------------------------------------------------------------
 // knn_gather: one thread per output element (flat over B E U: the stores are coalesced, the U reads of an entry are
@@ -64,7 +46,7 @@ __global__ __launch_bounds__(256) void knn_gather_kernel(const float* __restrict
     }
     const unsigned b = ent / (unsigned)E;
     const int64_t j = idx[ent];
-    out[f] = kso_valid(j, M) ? x[((size_t)b * M + (size_t)j) * U + c] : __builtin_nanf("");
+    out[f] = dl_valid(j, M) ? x[((size_t)b * M + (size_t)j) * U + c] : __builtin_nanf("");
   }
 }
 
@@ -77,7 +59,7 @@ __global__ __launch_bounds__(256) void knn_gather3_kernel(const float* __restric
   const int b = t / E;
   const int64_t j = idx[t];
   float v0 = __builtin_nanf(""), v1 = v0, v2 = v0;
-  if (kso_valid(j, M)) {
+  if (dl_valid(j, M)) {
     const float* X = x + ((size_t)b * M + (size_t)j) * 3;
     v0 = X[0];
     v1 = X[1];
@@ -87,124 +69,6 @@ __global__ __launch_bounds__(256) void knn_gather3_kernel(const float* __restric
   O[0] = v0;
   O[1] = v1;
   O[2] = v2;
-}
-
-// ------------------------------------------------------------------------------------------
-// the counting sort of the entries by destination.  t: flat entry number over the batch (B E < 2^31), d: flat destination
-// number (B M < 2^31).
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kso_count_kernel(const int64_t* __restrict__ idx, int E, int M, int BE,
-                                                        int* __restrict__ start) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= BE) return;
-  const int b = t / E;
-  const int64_t j = idx[t];
-  if (kso_valid(j, M)) atomicAdd(start + (size_t)b * (M + 1) + (int)j, 1);
-}
-
-__global__ __launch_bounds__(256) void kso_scan_kernel(int* __restrict__ start, int* __restrict__ cursor, int M) {
-  __shared__ int s_w[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int* S = start + (size_t)b * (M + 1);
-  int* Cu = cursor + (size_t)b * M;
-  int carry = 0;
-  for (int i0 = 0; i0 < M; i0 += 256) {
-    const int i = i0 + tid;
-    const int v = i < M ? S[i] : 0;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) s_w[wave] = x;
-    __syncthreads();
-    int base = carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) base += s_w[w];
-      total += s_w[w];
-    }
-    if (i < M) {
-      S[i] = base + x - v;
-      Cu[i] = base + x - v;
-    }
-    carry += total;
-    __syncthreads();
-  }
-  if (tid == 0) S[M] = carry;
-}
-
-__global__ __launch_bounds__(256) void kso_place_kernel(const int64_t* __restrict__ idx, int E, int M, int BE,
-                                                        int* __restrict__ cursor, int* __restrict__ bucket) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= BE) return;
-  const int b = t / E, e = t - b * E;
-  const int64_t j = idx[t];
-  if (!kso_valid(j, M)) return;
-  const int pos = atomicAdd(cursor + (size_t)b * M + (int)j, 1);   // < start[j + 1] <= E: the counts were taken from the same idx
-  bucket[(size_t)b * E + pos] = e;
-}
-
-// One wavefront per destination (four per workgroup); the segments of more than 64 entries are then ranked by the whole
-// workgroup, one after the other.  No thread leaves before the last barrier.
-__global__ __launch_bounds__(256) void kso_sort_kernel(const int* __restrict__ start, const int* __restrict__ bucket,
-                                                       int* __restrict__ order, int E, int M, int BM) {
-  __shared__ int s_tile[KSO_TILE];
-  __shared__ int s_len[4];
-  __shared__ size_t s_off[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int d = blockIdx.x * 4 + wave;
-  int L = 0;
-  size_t off = 0;
-  if (d < BM) {
-    const int b = d / M, i = d - b * M;
-    const int* S = start + (size_t)b * (M + 1);
-    const int s0 = S[i];
-    L = S[i + 1] - s0;
-    off = (size_t)b * E + s0;
-  }
-  if (L > 0 && L <= 64) {
-    const int key = lane < L ? bucket[off + lane] : INT_MAX;
-    int r = 0;
-    for (int k = 0; k < L; ++k) r += __shfl(key, k, 64) < key ? 1 : 0;
-    if (lane < L) order[off + r] = key;
-  }
-  if (lane == 0) {
-    s_len[wave] = L > 64 ? L : 0;
-    s_off[wave] = off;
-  }
-  __syncthreads();
-  for (int w = 0; w < 4; ++w) {
-    const int Lw = s_len[w];   // (the same value in every thread: the loops and barriers below are uniform)
-    if (Lw == 0) continue;
-    const int* in = bucket + s_off[w];
-    int* out = order + s_off[w];
-    for (int q0 = 0; q0 < Lw; q0 += 256 * KSO_KPT) {
-      int key[KSO_KPT], r[KSO_KPT];
-#pragma unroll
-      for (int u = 0; u < KSO_KPT; ++u) {
-        const int q = q0 + u * 256 + tid;
-        key[u] = q < Lw ? in[q] : INT_MIN;   // (nothing is smaller than INT_MIN: such a slot counts nothing and writes nothing)
-        r[u] = 0;
-      }
-      for (int t0 = 0; t0 < Lw; t0 += KSO_TILE) {
-        const int tn = min(KSO_TILE, Lw - t0);
-        __syncthreads();
-        for (int k = tid; k < tn; k += 256) s_tile[k] = in[t0 + k];
-        __syncthreads();
-#pragma unroll 8
-        for (int k = 0; k < tn; ++k) {
-          const int v = s_tile[k];   // the same address in every lane: a broadcast read
-#pragma unroll
-          for (int u = 0; u < KSO_KPT; ++u) r[u] += v < key[u] ? 1 : 0;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < KSO_KPT; ++u)
-        if (q0 + u * 256 + tid < Lw) out[r[u]] = key[u];   // r < Lw: a rank among Lw distinct entries
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -262,7 +126,7 @@ __global__ __launch_bounds__(256) void kpg_g1_kernel(const float* __restrict__ p
   float sx = 0.f, sy = 0.f, sz = 0.f;
   for (int k = 0; k < K; ++k) {
     const int64_t j = I[k];
-    if (!kso_valid(j, N2)) continue;
+    if (!dl_valid(j, N2)) continue;
     const float* Q = R + (size_t)j * 3;
     const float w = GD[k];
     sx = sx + kpg_term(w, ax, Q[0]);
@@ -308,113 +172,8 @@ __global__ __launch_bounds__(256) void kpg_g2_kernel(const float* __restrict__ p
 }
 
 // ------------------------------------------------------------------------------------------
-// The same steps with the tables of ONE instance in LDS: one workgroup of KSL_T threads per instance.
-//   LDS (int32): start [M+1] | cursor [M] | bucket [E] | order [E] | long [E / 65 + 1]
-// `long` lists the destinations with more than 64 entries (at most E / 65 of them; the order of the list does not matter:
-// every segment's result is unique); the workgroup ranks them one after the other, KSL_KPT entries per thread and pass,
-// reading the segment straight from LDS (the same address in every lane: broadcast reads).
+// the same sums behind ksl_build: one workgroup of KSL_T threads per instance, its lists in LDS
 // ------------------------------------------------------------------------------------------
-constexpr int KSL_T = 1024;
-constexpr int KSL_KPT = 4;
-constexpr size_t KSL_LDS_MAX = 160 * 1024 - 1024;   // dynamic LDS (the static wave partials beside it)
-
-size_t ksl_lds_bytes(int E, int M) { return sizeof(int) * ((size_t)(M + 1) + M + 2 * (size_t)E + E / 65 + 1); }
-
-struct KslLists {
-  const int* start;
-  const int* order;
-};
-
-__device__ __forceinline__ KslLists ksl_build(const int64_t* __restrict__ I, int E, int M, int* sm) {
-  __shared__ int s_w[KSL_T / 64];
-  __shared__ int s_nlong;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int* s_start = sm;
-  int* s_cursor = s_start + (M + 1);
-  int* s_bucket = s_cursor + M;
-  int* s_order = s_bucket + E;
-  int* s_long = s_order + E;
-  for (int i = tid; i <= M; i += KSL_T) s_start[i] = 0;
-  if (tid == 0) s_nlong = 0;
-  __syncthreads();
-  for (int e = tid; e < E; e += KSL_T) {
-    const int64_t j = I[e];
-    if (kso_valid(j, M)) atomicAdd(s_start + (int)j, 1);
-  }
-  __syncthreads();
-  int carry = 0;
-  for (int i0 = 0; i0 < M; i0 += KSL_T) {
-    const int i = i0 + tid;
-    const int v = i < M ? s_start[i] : 0;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) s_w[wave] = x;
-    __syncthreads();
-    int base = carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < KSL_T / 64; ++w) {
-      if (w < wave) base += s_w[w];
-      total += s_w[w];
-    }
-    if (i < M) {
-      s_start[i] = base + x - v;
-      s_cursor[i] = base + x - v;
-    }
-    carry += total;
-    __syncthreads();
-  }
-  if (tid == 0) s_start[M] = carry;
-  __syncthreads();
-  for (int e = tid; e < E; e += KSL_T) {
-    const int64_t j = I[e];
-    if (!kso_valid(j, M)) continue;
-    const int pos = atomicAdd(s_cursor + (int)j, 1);   // < start[j + 1] <= E: the counts were taken from the same idx
-    s_bucket[pos] = e;
-  }
-  __syncthreads();
-  for (int i = wave; i < M; i += KSL_T / 64) {
-    const int s0 = s_start[i], L = s_start[i + 1] - s0;
-    if (L <= 0) continue;
-    if (L <= 64) {
-      const int key = lane < L ? s_bucket[s0 + lane] : INT_MAX;
-      int r = 0;
-      for (int k = 0; k < L; ++k) r += s_bucket[s0 + k] < key ? 1 : 0;
-      if (lane < L) s_order[s0 + r] = key;
-    } else if (lane == 0) {
-      s_long[atomicAdd(&s_nlong, 1)] = i;   // at most E / 65 segments hold more than 64 of the E entries
-    }
-  }
-  __syncthreads();
-  const int nlong = s_nlong;
-  for (int q = 0; q < nlong; ++q) {
-    const int i = s_long[q];
-    const int s0 = s_start[i], L = s_start[i + 1] - s0;
-    for (int p0 = 0; p0 < L; p0 += KSL_T * KSL_KPT) {
-      int key[KSL_KPT], r[KSL_KPT];
-#pragma unroll
-      for (int u = 0; u < KSL_KPT; ++u) {
-        const int p = p0 + u * KSL_T + tid;
-        key[u] = p < L ? s_bucket[s0 + p] : INT_MIN;   // (nothing is smaller than INT_MIN: counts nothing, writes nothing)
-        r[u] = 0;
-      }
-      for (int k = 0; k < L; ++k) {
-        const int v = s_bucket[s0 + k];
-#pragma unroll
-        for (int u = 0; u < KSL_KPT; ++u) r[u] += v < key[u] ? 1 : 0;
-      }
-#pragma unroll
-      for (int u = 0; u < KSL_KPT; ++u)
-        if (p0 + u * KSL_T + tid < L) s_order[s0 + r[u]] = key[u];   // r < L: a rank among L distinct entries
-    }
-  }
-  __syncthreads();
-  return KslLists{s_start, s_order};
-}
-
 __global__ __launch_bounds__(KSL_T) void kgg_lds_kernel(const float* __restrict__ g, const int64_t* __restrict__ idx, int E,
                                                         int M, int U, float* __restrict__ gx) {
 #pragma clang fp contract(off)
@@ -480,23 +239,6 @@ int kso_sizes(int B, int M, int L, int K, int* E) {
   return GEOA3_OK;
 }
 
-// steps 1-4: `scratch` <- the lists of the B x M destinations
-int kso_build(const int64_t* idx, int B, int E, int M, void* scratch, hipStream_t s, int** start_out, int** order_out) {
-  const int BE = B * E, BM = B * M;
-  int* start = static_cast<int*>(scratch);
-  int* cursor = start + (size_t)B * (M + 1);
-  int* bucket = cursor + (size_t)B * M;
-  int* order = bucket + (size_t)B * E;
-  if (hipMemsetAsync(start, 0, (size_t)B * (M + 1) * sizeof(int), s) != hipSuccess) return GEOA3_ELAUNCH;
-  hipLaunchKernelGGL(kso_count_kernel, dim3((BE + 255) / 256), dim3(256), 0, s, idx, E, M, BE, start);
-  hipLaunchKernelGGL(kso_scan_kernel, dim3(B), dim3(256), 0, s, start, cursor, M);
-  hipLaunchKernelGGL(kso_place_kernel, dim3((BE + 255) / 256), dim3(256), 0, s, idx, E, M, BE, cursor, bucket);
-  hipLaunchKernelGGL(kso_sort_kernel, dim3((BM + 3) / 4), dim3(256), 0, s, start, bucket, order, E, M, BM);
-  *start_out = start;
-  *order_out = order;
-  return GEOA3_OK;
-}
-
 }  // namespace
 
 extern "C" int geoa3_knn_gather(const float* x, const int64_t* idx, int B, int M, int L, int K, int U, float* out,
@@ -522,7 +264,7 @@ extern "C" int geoa3_knn_gather(const float* x, const int64_t* idx, int B, int M
 extern "C" int64_t geoa3_knn_scatter_scratch_bytes(int B, int E, int M) {
   int e = 0;
   if (E <= 0 || kso_sizes(B, M, E, 1, &e) != GEOA3_OK) return -1;
-  return (int64_t)sizeof(int) * B * ((int64_t)(M + 1) + M + 2 * (int64_t)E);
+  return (int64_t)dest_lists_scratch_bytes(B, E, M);
 }
 
 extern "C" int geoa3_knn_gather_grad(const float* g, const int64_t* idx, int B, int M, int L, int K, int U, float* gx,
@@ -542,8 +284,8 @@ extern "C" int geoa3_knn_gather_grad(const float* g, const int64_t* idx, int B, 
     GEOA3_CHECK_LAUNCH();
     return GEOA3_OK;
   }
-  int *start = nullptr, *order = nullptr;
-  const int rb = kso_build(idx, B, E, M, scratch, s, &start, &order);
+  const int *start = nullptr, *order = nullptr;
+  const int rb = launch_dest_lists(idx, B, E, M, scratch, s, &start, &order);
   if (rb != GEOA3_OK) return rb;
   const int BM = B * M;
   hipLaunchKernelGGL(kgg_sum_kernel, dim3((BM + 255) / 256, cg), dim3(256), 0, s, g, start, order, E, M, U, BM, gx);
@@ -569,8 +311,8 @@ extern "C" int geoa3_knn_points_grad(const float* p1, const float* p2, const int
                                 (int)lds);
     hipLaunchKernelGGL(kpg_g2_lds_kernel, dim3(B), dim3(KSL_T), lds, s, p1, p2, idx, gd, N1, N2, K, g2);
   } else if (g2) {
-    int *start = nullptr, *order = nullptr;
-    const int rb = kso_build(idx, B, E, N2, scratch, s, &start, &order);
+    const int *start = nullptr, *order = nullptr;
+    const int rb = launch_dest_lists(idx, B, E, N2, scratch, s, &start, &order);
     if (rb != GEOA3_OK) return rb;
     const int BN2 = B * N2;
     hipLaunchKernelGGL(kpg_g2_kernel, dim3((BN2 + 255) / 256), dim3(256), 0, s, p1, p2, gd, start, order, N1, N2, K, BN2, g2);

@@ -11,12 +11,12 @@
 //   * three_interpolate (:72-101): out = (p[i1] * w1 + p[i2] * w2) + p[i3] * w3.
 //   * three_interpolate_grad (:116-143): grad_points[b][c][i] = sum over the (j, slot) with idx[b][j][slot] == i of
 //     grad_out[b][c][j] * weight[b][j][slot].  The reference scatters with float atomics (the order of the sum, and so its
-//     bits, change from run to run); here every destination sums ITS list in ascending (j, slot) order: the same bits on
-//     every call and for every batch an instance is part of.
+//     bits, change from run to run); here every destination sums ITS list in ascending (j, slot) order (dest_lists.h): the
+//     same bits on every call and for every batch an instance is part of.
 // Rounding: un-fused by default (every product and sum rounded to float32, the CPU oracle's order); GEOA3_PN2_CONTRACT (the
 // *_ex entry points) selects fmaf(dz, dz, fmaf(dy, dy, dx * dx)) / fmaf(p3, w3, fmaf(p2, w2, p1 * w1)), what nvcc's default
 // -fmad=true most likely made of :33 and :98-99 -- the convention of geoa3_pn2_ball_query_ex.
-#include <climits>
+#include "dest_lists.h"
 #include "pointnet_kernels.h"
 
 namespace {
@@ -128,96 +128,14 @@ __global__ __launch_bounds__(256) void three_interpolate_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------
-// three_interpolate_grad: the 3n entries e = 3 j + slot of an instance are sorted by destination (a counting sort into the
-// caller's scratch), then one thread per (destination, group of TG_CG channels) sums its list in ascending e.
-//   scratch (int32): start [B][m+1] | cursor [B][m] | bucket [B][3n] | order [B][3n]
-//   1. tig_count:  start[b][i] = number of entries that point at i (integer atomics: a count has no order)
-//   2. tig_scan:   start <- its exclusive prefix sum (one workgroup per instance), cursor <- start
-//   3. tig_place:  every entry takes the next free place of its destination's segment of `bucket` (integer atomic cursor:
-//                  the ORDER inside a segment depends on timing ...)
-//   4. tig_sort:   ... so one wavefront per destination sorts its segment by e into `order` (the entries are distinct:
-//                  the result is unique).  Rank sort: the rank of an entry is the number of smaller ones in the segment --
-//                  through lane shuffles up to 64 entries, by re-reading the segment (same address in every lane) above.
-//                  Quadratic in the list's length, which is 3n / m on average.
-//   5. tig_sum:    grad_points[b][c][i] = sum over order[start[i] .. start[i+1]) of fl(grad_out[b][c][e / 3] * weight[b][e]),
-//                  each product rounded, added in list order; an empty list writes 0.  Every element is written.
+// three_interpolate_grad: the 3n entries e = 3 j + slot of an instance are sorted by destination into the caller's scratch
+// (launch_dest_lists, dest_lists.h), then one thread per (destination, group of TG_CG channels) sums its list in ascending e:
+//   tig_sum:  grad_points[b][c][i] = sum over order[start[i] .. start[i+1]) of fl(grad_out[b][c][e / 3] * weight[b][e]),
+//             each product rounded, added in list order; an empty list writes +0.0.  Every element is written.
 // No float atomics; a NaN or inf product is added like any other value and comes out as NaN / inf.
 // An index outside [0, m) (the caller's error, as in the reference) is not wrapped: its entry is in no list.
 // ------------------------------------------------------------------------------------------
 constexpr int TG_CG = 8;   // channels per thread of tig_sum
-
-__global__ __launch_bounds__(256) void tig_count_kernel(const int32_t* __restrict__ idx, int n3, int m, int* __restrict__ start) {
-  const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n3) return;
-  const int i = idx[(size_t)b * n3 + e];
-  if ((unsigned)i < (unsigned)m) atomicAdd(start + (size_t)b * (m + 1) + i, 1);
-}
-
-__global__ __launch_bounds__(256) void tig_scan_kernel(int* __restrict__ start, int* __restrict__ cursor, int m) {
-  __shared__ int s_w[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int* S = start + (size_t)b * (m + 1);
-  int* Cu = cursor + (size_t)b * m;
-  int carry = 0;
-  for (int i0 = 0; i0 < m; i0 += 256) {
-    const int i = i0 + tid;
-    const int v = i < m ? S[i] : 0;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) s_w[wave] = x;
-    __syncthreads();
-    int base = carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) base += s_w[w];
-      total += s_w[w];
-    }
-    if (i < m) {
-      S[i] = base + x - v;
-      Cu[i] = base + x - v;
-    }
-    carry += total;
-    __syncthreads();
-  }
-  if (tid == 0) S[m] = carry;
-}
-
-__global__ __launch_bounds__(256) void tig_place_kernel(const int32_t* __restrict__ idx, int n3, int m, int* __restrict__ cursor,
-                                                        int* __restrict__ bucket) {
-  const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n3) return;
-  const int i = idx[(size_t)b * n3 + e];
-  if ((unsigned)i >= (unsigned)m) return;
-  const int pos = atomicAdd(cursor + (size_t)b * m + i, 1);   // < start[i + 1] <= 3n: the counts were taken from the same idx
-  bucket[(size_t)b * n3 + pos] = e;
-}
-
-__global__ __launch_bounds__(256) void tig_sort_kernel(const int* __restrict__ start, const int* __restrict__ bucket,
-                                                       int* __restrict__ order, int n3, int m) {
-  const int b = blockIdx.y, i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (i >= m) return;
-  const int* S = start + (size_t)b * (m + 1);
-  const int s0 = S[i], L = S[i + 1] - s0;
-  const int* in = bucket + (size_t)b * n3 + s0;
-  int* out = order + (size_t)b * n3 + s0;
-  if (L <= 64) {
-    const int key = lane < L ? in[lane] : INT_MAX;
-    int r = 0;
-    for (int k = 0; k < L; ++k) r += __shfl(key, k, 64) < key ? 1 : 0;
-    if (lane < L) out[r] = key;
-  } else {
-    for (int q = lane; q < L; q += 64) {
-      const int key = in[q];
-      int r = 0;
-      for (int k = 0; k < L; ++k) r += in[k] < key ? 1 : 0;
-      out[r] = key;
-    }
-  }
-}
 
 __global__ __launch_bounds__(256) void tig_sum_kernel(const float* __restrict__ grad_out, const float* __restrict__ weight,
                                                       const int* __restrict__ start, const int* __restrict__ order, int C, int n,
@@ -303,7 +221,7 @@ extern "C" int geoa3_pn2_three_interpolate_ex(const float* points, const int32_t
 
 extern "C" int64_t geoa3_pn2_three_interpolate_scratch_bytes(int B, int n, int m) {
   if (B <= 0 || n <= 0 || m <= 0 || n > (INT_MAX - 255) / 3 || m > INT_MAX - 256) return -1;
-  return (int64_t)sizeof(int) * B * ((int64_t)(m + 1) + m + 6 * (int64_t)n);
+  return (int64_t)dest_lists_scratch_bytes(B, 3 * n, m);
 }
 
 extern "C" int geoa3_pn2_three_interpolate_grad(const float* grad_out, const int32_t* idx, const float* weight, int B, int C,
@@ -313,16 +231,9 @@ extern "C" int geoa3_pn2_three_interpolate_grad(const float* grad_out, const int
   const int cg = (C + TG_CG - 1) / TG_CG;
   if (cg > MAX_GRID_YZ) return GEOA3_ENOSUPPORT;
   hipStream_t s = geoa3_stream(stream);
-  const int n3 = 3 * n;
-  int* start = static_cast<int*>(scratch);
-  int* cursor = start + (size_t)B * (m + 1);
-  int* bucket = cursor + (size_t)B * m;
-  int* order = bucket + (size_t)B * n3;
-  if (hipMemsetAsync(start, 0, (size_t)B * (m + 1) * sizeof(int), s) != hipSuccess) return GEOA3_ELAUNCH;
-  hipLaunchKernelGGL(tig_count_kernel, dim3((n3 + 255) / 256, B), dim3(256), 0, s, idx, n3, m, start);
-  hipLaunchKernelGGL(tig_scan_kernel, dim3(B), dim3(256), 0, s, start, cursor, m);
-  hipLaunchKernelGGL(tig_place_kernel, dim3((n3 + 255) / 256, B), dim3(256), 0, s, idx, n3, m, cursor, bucket);
-  hipLaunchKernelGGL(tig_sort_kernel, dim3((m + 3) / 4, B), dim3(256), 0, s, start, bucket, order, n3, m);
+  const int *start = nullptr, *order = nullptr;
+  const int rb = launch_dest_lists(idx, B, 3 * n, m, scratch, s, &start, &order);
+  if (rb != GEOA3_OK) return rb;
   hipLaunchKernelGGL(tig_sum_kernel, dim3((m + 255) / 256, cg, B), dim3(256), 0, s, grad_out, weight, start, order, C, n, m,
                      grad_points);
   GEOA3_CHECK_LAUNCH();

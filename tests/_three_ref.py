@@ -7,6 +7,8 @@ TEST INFRASTRUCTURE, NOT PRODUCT CODE.  Written from the semantics, not from the
     three_interpolate        (p[i1] * w1 + p[i2] * w2) + p[i3] * w3 in float32, or fmaf(p3, w3, fmaf(p2, w2, p1 * w1))
     three_interpolate_grad64 the scatter sum in float64, with the contributor count and sum |g * w| per element (the terms
                              of the float32 summation bound)
+    three_interpolate_grad32 the scatter sum as the library promises it: sequential in float32 from +0.0, in ascending
+                             entry number e = 3 j + slot, each product rounded
 
 numpy arrays in, numpy arrays out; the `*_t` forms take and return torch CPU tensors (what the golden generator registers
 as the missing attributes of the `pointnet2_ops._ext` stand-in).
@@ -78,6 +80,27 @@ def three_interpolate_grad64(grad_out, idx, weight, m: int):
                     np.add.at(mag[b, c], idx[b, :, s], np.abs(t[c]))
                 np.add.at(cnt[b, 0], idx[b, :, s], 1)
     return out, cnt, mag
+
+
+def three_interpolate_grad32(grad_out, idx, weight, m: int, descending: bool = False):
+    """grad_out [B,C,n], idx / weight [B,n,3] -> grad_points [B,C,m] float32: the sum the library promises, bit for bit.
+    A float32 loop over the entries e = 3 j + slot in ascending order, from +0.0:
+    out[b,:,i] = fl(out[b,:,i] + fl(g[b,:,j] * w[b,e])); an entry whose index is outside [0, m) is dropped.
+    `descending` walks the same entries backwards (tests only: what a wrong order does to the bits)."""
+    f = np.float32
+    g = np.asarray(grad_out, dtype=f)
+    B, C, n = g.shape
+    w = np.asarray(weight, dtype=f).reshape(B, 3 * n)
+    idx = np.asarray(idx).astype(np.int64).reshape(B, 3 * n)
+    out = np.zeros((B, C, m), dtype=f)
+    entries = range(3 * n - 1, -1, -1) if descending else range(3 * n)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(B):
+            for e in entries:
+                i = idx[b, e]
+                if 0 <= i < m:
+                    out[b, :, i] = out[b, :, i] + g[b, :, e // 3] * w[b, e]     # float32 arrays: each operation rounds once
+    return out
 
 
 # ---- torch CPU forms with the signatures of interpolate.cpp (for the golden generator)

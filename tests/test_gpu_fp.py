@@ -4,7 +4,8 @@ geoa3_amd.pointnet2.ext, the autograd Functions and PointnetFPModule) against th
 
 Bars: three_nn and three_interpolate are bit-equal in both roundings.  three_interpolate_grad against the float64 sum:
 |got - ref| <= (count + 2) * 2^-24 * sum |g * w| per element, the float32 summation bound (count products each rounded
-once, count - 1 additions).  Values that pass through torch on both sides in another order (sqrt, the weights, the MLP):
+once, count - 1 additions) -- and bit-equal to the float32 loop in ascending entry number, the order the header
+promises (three_interpolate_grad32).  Values that pass through torch on both sides in another order (sqrt, the weights, the MLP):
 1e-4 * max |ref|, the bar of tests/test_gpu_uniform.py for float32 results summed in another order."""
 import os
 
@@ -162,6 +163,68 @@ def test_three_interpolate_grad_within_summation_bound(kind, C):
     for b in range(3):
         alone = ext.three_interpolate_grad(gc[b:b + 1].contiguous(), ic[b:b + 1].contiguous(), wc[b:b + 1].contiguous(), m)
         assert torch.equal(alone.view(torch.int32)[0], out.view(torch.int32)[b]), b
+
+
+def _hub_inputs():
+    """B = 2, n = 500 (1500 entries), m = 20, C = 3.  Instance 0: every entry on destination 7 (longer than a wavefront,
+    longer than one 1024-entry tile of the sort); instance 1: exactly 64 random entries on destination 3, exactly 65 on 11,
+    the other 1371 on 7.  Nobody else receives anything."""
+    rng = np.random.default_rng(77)
+    B, n, m, C = 2, 500, 20, 3
+    idx = np.full((B, 3 * n), 7, dtype=np.int32)
+    perm = rng.permutation(3 * n)
+    idx[1, perm[:64]] = 3
+    idx[1, perm[64:129]] = 11
+    weight = rng.random((B, n, 3)).astype(np.float32)
+    weight /= weight.sum(2, keepdims=True)
+    g = rng.standard_normal((B, C, n)).astype(np.float32)
+    return g, idx.reshape(B, n, 3), weight, m
+
+
+def _grad_on_gpu(g, idx, weight, m):
+    from geoa3_amd.pointnet2 import ext
+    out = ext.three_interpolate_grad(T(g).cuda(), T(idx).cuda(), T(weight).cuda(), m)
+    assert out.shape == (g.shape[0], g.shape[1], m) and out.dtype == torch.float32
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("C", [1, 8, 9, 65])
+@pytest.mark.parametrize("kind", ["same3", "sparse"])
+def test_three_interpolate_grad_bit_equal_to_ascending_float32_loop(kind, C):
+    """The promised order, not only the bound: every element has the bits of the float32 loop over e = 3 j + slot ascending
+    (tests/test_three_ref.py: the same loop descending changes bits in every one of these cases).  C on both sides of one
+    thread's group of 8 channels; "same3": lists of 300 entries (longer than a wavefront), "sparse": lists of 0 to ~10."""
+    g, idx, weight, m = _grad_inputs(kind, C, seed=40 + C)
+    got = _grad_on_gpu(g, idx, weight, m)
+    assert np.array_equal(_bits(got), _bits(R.three_interpolate_grad32(g, idx, weight, m)))
+
+
+def test_three_interpolate_grad_hub_exact_wavefront_and_untouched_rows():
+    """_hub_inputs: lists of 1500 and 1371 entries (more than one tile of the sort), of exactly 64 (the last length one
+    wavefront ranks) and exactly 65 (the first the workgroup ranks), and 17 / 19 empty lists per instance, which read +0.0
+    with no bit set."""
+    g, idx, weight, m = _hub_inputs()
+    cnt = np.stack([np.bincount(idx[b].ravel(), minlength=m) for b in range(2)])
+    assert cnt[0, 7] == 1500 and (cnt[1, 3], cnt[1, 11], cnt[1, 7]) == (64, 65, 1371) and cnt.sum() == 3000
+    got = _grad_on_gpu(g, idx, weight, m)
+    assert np.array_equal(_bits(got), _bits(R.three_interpolate_grad32(g, idx, weight, m)))
+    quiet = np.broadcast_to((cnt == 0)[:, None, :], got.shape)
+    assert quiet.sum() == 3 * (19 + 17) and not _bits(got)[quiet].any()
+    assert (got[~quiet] != 0).all()
+
+
+def test_three_interpolate_grad_drops_indices_out_of_range():
+    """An index of -1 and one of m (the caller's error) are in no list: their products are in no sum, every other sum is
+    the restatement's, bit for bit."""
+    g, idx, weight, m = _grad_inputs("sparse", 9, seed=60)
+    idx[0, 3, 1] = -1
+    idx[2, 64, 2] = m          # the last entry of the batch
+    want = R.three_interpolate_grad32(g, idx, weight, m)
+    ok = (idx >= 0) & (idx < m)
+    clean = R.three_interpolate_grad32(g, np.where(ok, idx, 0), np.where(ok, weight, np.float32(0)), m)
+    assert ok.sum() == idx.size - 2 and np.array_equal(want, clean)   # (g finite: a product with weight 0 adds +-0.0)
+    got = _grad_on_gpu(g, idx, weight, m)
+    assert np.array_equal(_bits(got), _bits(want))
 
 
 @pytest.mark.parametrize("kind", ["same3", "sparse"])

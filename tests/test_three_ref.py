@@ -97,3 +97,38 @@ def test_nan_and_inf_distances_are_never_selected():
     unknown[0, 2, 0] = np.nan
     d2, idx = R.three_nn(unknown, known)
     assert np.isposinf(d2[0, 2]).all() and not idx[0, 2].any()
+
+
+# ------------------------------------------------------------------------------------------ three_interpolate_grad32
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+@pytest.mark.parametrize("C", [1, 65])
+@pytest.mark.parametrize("kind", ["same3", "sparse"])
+def test_grad32_stays_within_the_summation_bound_of_the_float64_sum(kind, C):
+    from tests.test_gpu_fp import _grad_inputs
+    g, idx, weight, m = _grad_inputs(kind, C, seed=40 + C)
+    ref, cnt, mag = R.three_interpolate_grad64(g, idx, weight, m)
+    out = R.three_interpolate_grad32(g, idx, weight, m)
+    assert out.dtype == np.float32 and out.shape == ref.shape
+    assert (np.abs(out.astype(np.float64) - ref) <= (cnt + 2) * 2.0 ** -24 * mag).all()
+    assert not _bits(out)[np.broadcast_to(cnt == 0, out.shape)].any()   # +0.0 where nobody points
+
+
+@pytest.mark.parametrize("kind,C", [(k, c) for k in ("same3", "sparse") for c in (1, 8, 9, 65)] + [("hub", 3)])
+def test_grad32_bits_depend_on_the_order(kind, C):
+    """The bit test of tests/test_gpu_fp.py can see an order error: the same loop over DESCENDING e changes the bits of at
+    least one element on every input that test uses (and stays within the summation bound, which no order can miss)."""
+    from tests.test_gpu_fp import _grad_inputs, _hub_inputs
+    if kind == "hub":
+        g, idx, weight, m = _hub_inputs()
+    else:
+        g, idx, weight, m = _grad_inputs(kind, C, seed=40 + C)
+    up = R.three_interpolate_grad32(g, idx, weight, m)
+    down = R.three_interpolate_grad32(g, idx, weight, m, descending=True)
+    changed = int((_bits(up) != _bits(down)).sum())
+    print("three_interpolate_grad32 %s C=%d: %d of %d elements change bits in descending order" % (kind, g.shape[1], changed, up.size))
+    assert changed > 0
+    ref, cnt, mag = R.three_interpolate_grad64(g, idx, weight, m)
+    assert (np.abs(down.astype(np.float64) - ref) <= (cnt + 2) * 2.0 ** -24 * mag).all()

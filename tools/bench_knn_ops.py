@@ -4,7 +4,9 @@ composition they replace.
 
     python tools/bench_knn_ops.py [--repeats 7] [--iters 100] [--out profiles/knn_ops_bench.txt]
 
-B = 250, n1 = n2 = 1024, K = 1 and K = 17 (the 1-NN tables and the k = 16 curvature table of the reference's objective).
+B = 250, n1 = n2 = 1024, K = 1 and K = 17 (the 1-NN tables and the k = 16 curvature table of the reference's objective: the
+backward passes build their lists in LDS), and B = 64, n1 = n2 = 2048, K = 17 (the backward passes alone: an instance's
+tables no longer fit LDS, the lists go through scratch).
 Device events around `iters` calls after warm-up, the median (min .. max) of `repeats` such windows, the two forms timed in
 alternation.  Per K:
   gather          out = knn_gather(x [B,n,3], idx)                       | torch.gather over the expanded index
@@ -75,13 +77,7 @@ def main():
     from oracle import geoa3_oracle as O
     assert torch.cuda.is_available(), "bench_knn_ops.py measures on the GPU"
     dev = torch.device("cuda")
-    B, n = 250, 1024
-    ori, nrm = O.make_synthetic_clouds(B, n, seed=0)
-    adv = (ori + 0.01 * torch.randn(ori.shape, generator=torch.Generator().manual_seed(1))).to(dev).contiguous()
-    ori, nrm = ori.to(dev), nrm.to(dev)
-    p1, p2 = adv.permute(0, 2, 1).contiguous(), ori.permute(0, 2, 1).contiguous()
-    lines = ["knn_gather / knn_points operators, B=%d n1=n2=%d, us per call: median (min .. max) of %d windows of %d calls"
-             % (B, n, a.repeats, a.iters), "%-4s %-11s %-30s %-30s %s" % ("K", "what", "library", "torch composition", "library/torch")]
+    lines = []
 
     def compare(K, what, new, old):
         for fn in (new, old):
@@ -97,7 +93,18 @@ def main():
                                                      statistics.median(t[0]) / statistics.median(t[1])))
         print(lines[-1], flush=True)
 
-    for K in (1, 17):
+    # B = 250, n = 1024: the lists are built in LDS; B = 64, n = 2048, K = 17: 34816 entries per instance, 297 KB of tables --
+    # the form with the lists in scratch (backward passes only)
+    for B, n, K in ((250, 1024, 1), (250, 1024, 17), (64, 2048, 17)):
+        ori, nrm = O.make_synthetic_clouds(B, n, seed=0)
+        adv = (ori + 0.01 * torch.randn(ori.shape, generator=torch.Generator().manual_seed(1))).to(dev).contiguous()
+        ori, nrm = ori.to(dev), nrm.to(dev)
+        p1, p2 = adv.permute(0, 2, 1).contiguous(), ori.permute(0, 2, 1).contiguous()
+        if K == 1 or n != 1024:
+            lines += ["knn_gather / knn_points operators, B=%d n1=n2=%d, us per call: median (min .. max) of %d windows of %d calls"
+                      % (B, n, a.repeats, a.iters),
+                      "%-4s %-11s %-30s %-30s %s" % ("K", "what", "library", "torch composition", "library/torch")]
+            print("\n".join(lines[-2:]), flush=True)
         idx = (ops.knn_points(p1, p2, K=K) if K == 1 else ops.knn_points(p1, p1, K=K)).idx
         src = p2 if K == 1 else p1
         g4 = torch.randn(B, n, K, 3, device=dev)
@@ -106,11 +113,12 @@ def main():
         torch.testing.assert_close(torch.ops.geoa3.knn_gather_grad(g4, idx, n), torch_gather_bwd(g4, idx, n), rtol=1e-4, atol=1e-5)
         for x, y in zip(torch.ops.geoa3.knn_points_grad(p1, src, idx, gd), torch_points_bwd(p1, src, idx, gd)):
             torch.testing.assert_close(x, y, rtol=1e-4, atol=1e-5)
-        compare(K, "gather", lambda: torch.ops.geoa3.knn_gather(src, idx), lambda: torch_gather(src, idx))
+        if n == 1024:
+            compare(K, "gather", lambda: torch.ops.geoa3.knn_gather(src, idx), lambda: torch_gather(src, idx))
         compare(K, "gather_bwd", lambda: torch.ops.geoa3.knn_gather_grad(g4, idx, n), lambda: torch_gather_bwd(g4, idx, n))
         compare(K, "points_bwd", lambda: torch.ops.geoa3.knn_points_grad(p1, src, idx, gd),
                 lambda: torch_points_bwd(p1, src, idx, gd))
-        if K > 1:
+        if K > 1 and n == 1024:
             def step(gather):
                 x = adv.detach().requires_grad_()
                 kap, _ = kappa_adv(x, ori, nrm, K - 1, ops.knn_points, gather)
