@@ -170,6 +170,13 @@ SIGNATURES = {
                                              C.c_int, vp]),
     "geoa3_debug_fc_ex": (C.c_int, [vp, C.c_int, C.c_int64, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp, C.c_int,
                                     C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_debug_pn2_frag_image": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_debug_pn2_sa2_pre": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, vp]),
+    "geoa3_debug_pn2_sa2_fwd": (C.c_int, [vp] * 13 + [C.c_int, C.c_int, C.c_int, vp]),
+    "geoa3_debug_pn2_sa2b_scratch_bytes": (C.c_int64, [C.c_int]),
+    "geoa3_debug_pn2_sa2b": (C.c_int, [vp] * 14 + [C.c_int, vp]),
+    "geoa3_debug_pn2ssg_workspace_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
+                                                      C.c_int]),
     "geoa3_profile_enable": (C.c_int, [C.c_int]),
     "geoa3_profile_select": (C.c_int, [C.c_uint]),
     "geoa3_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_int]),

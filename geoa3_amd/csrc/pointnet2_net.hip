@@ -74,6 +74,7 @@ int pack_images(const geoa3_pn2ssg_weights& p, void* base, hipStream_t s) {
   return GEOA3_OK;
 }
 
+// (a new field also gets a name in geoa3_debug_pn2ssg_workspace_layout below, in carve()'s order: a static_assert there counts them)
 struct Ws {
   float *xyz, *nx1, *out1, *f1, *nx2, *r, *shift, *da0, *out2, *h1, *h2, *z3, *p3, *q1, *q2;
   int32_t *idx1, *gidx1, *idx2, *gidx2, *arg2, *arg3;
@@ -361,6 +362,29 @@ int fc(const float* X, int K, const float* W, const float* bias, float* Y, int N
 extern "C" int64_t geoa3_pn2ssg_workspace_bytes(int B, int N) {
   if (B <= 0 || N < MIN_N || N > MAX_N) return -1;
   return (int64_t)carve(nullptr, B, N).total;
+}
+
+// diagnostics (geoa3_hip_debug.h): names and byte offsets of the workspace's buffers, in address order
+extern "C" int geoa3_debug_pn2ssg_workspace_layout(int B, int N, const char** names, int64_t* offsets, int cap) {
+  if (B <= 0 || N < MIN_N || N > MAX_N || !names || !offsets) return -1;
+  char* const base = reinterpret_cast<char*>(static_cast<uintptr_t>(1) << 40);
+  const Ws w = carve(base, B, N);
+  const struct { const char* name; const void* p; } f[] = {
+      {"xyz", w.xyz}, {"idx1", w.idx1}, {"nx1", w.nx1}, {"gidx1", w.gidx1}, {"out1", w.out1}, {"arg1", w.arg1}, {"f1", w.f1},
+      {"idx2", w.idx2}, {"nx2", w.nx2}, {"gidx2", w.gidx2}, {"r", w.r}, {"shift", w.shift}, {"da0", w.da0}, {"out2", w.out2},
+      {"arg2", w.arg2}, {"h1", w.h1}, {"h2", w.h2}, {"z3", w.z3}, {"p3", w.p3}, {"arg3", w.arg3}, {"q1", w.q1}, {"q2", w.q2},
+      {"g256", w.g256}, {"g512", w.g512}, {"g1024", w.g1024}, {"dh2", w.dh2}, {"dh1", w.dh1}, {"dout2", w.dout2},
+      {"dnx2", w.dnx2}, {"d1", w.d1}, {"df1", w.df1}, {"dnx1", w.dnx1}, {"g1", w.g1}, {"gxyz", w.gxyz}, {"gnx1", w.gnx1},
+      {"bad", w.bad}, {"m0", w.m0}, {"m1", w.m1}, {"images", w.images}, {"end", base + w.total}};
+  // every member of Ws is one pointer-sized word (the buffers, then `total`): a field added to the struct without a name here
+  // does not compile
+  static_assert(sizeof(f) / sizeof(f[0]) == sizeof(Ws) / sizeof(void*), "name every field of Ws (and `end` for total)");
+  const int n = (int)(sizeof(f) / sizeof(f[0]));
+  for (int i = 0; i < n && i < cap; ++i) {
+    names[i] = f[i].name;
+    offsets[i] = (int64_t)(static_cast<const char*>(f[i].p) - base);
+  }
+  return n;
 }
 
 extern "C" int64_t geoa3_pn2ssg_images_bytes(void) { return (int64_t)img_off(IM_COUNT); }

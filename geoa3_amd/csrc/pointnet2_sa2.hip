@@ -361,7 +361,7 @@ struct Sa2PreArgs {
   int Np;                // XT: points per instance (a multiple of 32)
 };
 
-constexpr int sa2_pre_lds() { return S2_K * S2_K * 4 + 4 * 2 * 64 * 16; }
+constexpr int sa2_pre_lds() { return S2_K * S2_K * 4 + 4 * 2 * 64 * 16 + 16; }
 
 // XT: the same product with X channel-major (the backward's d f = W_f^T d r from the grouping gradient's layout, written
 // centroid-major for level 1's backward: again no transpose)
@@ -370,6 +370,7 @@ __global__ __launch_bounds__(256) void sa2_pre_kernel(Sa2PreArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s2_sm[];
   half8* s_w = reinterpret_cast<half8*>(s2_sm);                     // [(tile * 8 + c) * 2 + piece][lane]
   half8* s_wx = s_w + S2_K * S2_K * 4 / 16;                         // [tile * 2 + piece][lane]: the coordinates' k-step
+  int* s_big = reinterpret_cast<int*>(s_wx + 4 * 2 * 64);           // [tile]: its W_x does not fit the image's scale (below)
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   {
@@ -387,6 +388,14 @@ __global__ __launch_bounds__(256) void sa2_pre_kernel(Sa2PreArgs a) {
       x[1] = a.Wx[3 * co + 1];
       x[2] = a.Wx[3 * co + 2];
     }
+    // The image's scale is chosen from max|W_f| alone: an entry of W_x from ~4 max|W_f| on reaches fp16's infinity there
+    // (rn16 of 65520 and more), and hi = inf, lo = -inf make the whole row NaN.  A column tile that holds such an entry
+    // keeps ZEROS in its ninth k-step (exact zeros into the accumulator) and adds its coordinate term in fp32 behind the
+    // unscale (below).  Every other tile -- any W_x with max|W_x| <= max|W_f| -- computes the bits it always did.
+    const float wm = fmaxf(__builtin_fabsf(x[0]), fmaxf(__builtin_fabsf(x[1]), __builtin_fabsf(x[2]))) * sw;
+    const bool big = wave_max(wm) >= 65520.f;
+    if (big) x[0] = x[1] = x[2] = 0.f;
+    if (lane == 0) s_big[t] = big ? 1 : 0;
     half8 wh, wl;
     sf_split8(x, sw, wh, wl);
     s_wx[(t * 2 + 0) * 64 + lane] = wh;
@@ -451,6 +460,17 @@ __global__ __launch_bounds__(256) void sa2_pre_kernel(Sa2PreArgs a) {
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[c], bh, acc, 0, 0, 0);
       }
       // acc[r]: point p0 + (r & 3) + 8 (r >> 2) + 4 h, channel 32 t + l31: 128 contiguous bytes per point and half-wave
+      if (XYZ && __builtin_amdgcn_readfirstlane(s_big[t])) {   // (workgroup-uniform, and rare: a W_x beyond the image's range)
+        const float* wx = a.Wx + 3 * (32 * t + l31);
+        const float w0 = wx[0], w1 = wx[1], w2 = wx[2];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float* pz = a.xyz + (p0 + mfma_row(r, lane)) * 3;
+          Y[(size_t)mfma_row(r, lane) * S2_K + 32 * t] =
+              __builtin_fmaf(pz[2], w2, __builtin_fmaf(pz[1], w1, __builtin_fmaf(pz[0], w0, acc[r] * unscale)));
+        }
+        continue;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) Y[(size_t)mfma_row(r, lane) * S2_K + 32 * t] = acc[r] * unscale;
     }

@@ -133,6 +133,55 @@ int geoa3_debug_geo_wide(const geoa3_geo_args* args, int ranges, void* stream);
  * of buffers (names[i] are static strings). */
 int geoa3_debug_pointnet_workspace_layout(int B, int N, int classes, const char** names, int64_t* offsets, int cap);
 
+/* ------------------------------------------------------------------------------------------
+ * The kernels of PointNet++ SSG's second level one at a time (tests/test_gpu_pn2_kernels.py).  Each entry fills the launch
+ * arguments the way geoa3_pn2ssg_forward does and starts the kernel; GEOA3_EINVAL for a null pointer or a size outside the
+ * kernel's contract.  No entry can look at device data: every index of gidx must lie in [0, N1).
+ *
+ * Fragment image of W [R][K] (R % 32 == 0, K % 16 == 0): un[0] = 2^(E - 140) with E = the biased exponent of max|W| clamped
+ * to [14, 254] (the maximum times 1 / un lies in [2^13, 2^14)); img holds 2 R K fp16, the pieces hi = fp16(W / un) and
+ * lo = fp16(W / un - hi) at [row >> 5][k >> 4][piece][32 ((k >> 3) & 1) + (row & 31)][k & 7].
+ * ------------------------------------------------------------------------------------------ */
+int geoa3_debug_pn2_frag_image(const float* W, int R, int K, void* img, float* un, void* stream);
+/* Y [P][128] = X W_f^T (+ xyz W_x^T when xyz is given): X [P][128] point-major, or [P / Np][128][Np] when x_channel_major;
+ * xyz [P][3], W_x [128][3]; wf_img / wf_un = the fragment image of W_f [128][128].  P (and Np) multiples of 32. */
+int geoa3_debug_pn2_sa2_pre(const float* X, int x_channel_major, int Np, const float* xyz, const void* wf_img,
+                            const float* wf_un, const float* Wx, float* Y, int64_t P, void* stream);
+/* out [B][256][M] = relu(max_s W2 relu(W1 relu(rT[gidx] + shift) + b1) + b2), arg = the first maximal sample: rT [B][N1][128],
+ * gidx [B][M][64], shift [B][128][M], the images of W1 [128][128] and W2 [256][128]; m0 / m1 [B * M][64][4] 32-bit words:
+ * bit c of word w of a row (centre, sample) = channel 32 w + c of a0 / a1 is positive.  M a multiple of 8. */
+int geoa3_debug_pn2_sa2_fwd(const float* rT, const int32_t* gidx, const float* shift, const void* w1_img, const float* w1_un,
+                            const float* b1, const void* w2_img, const float* w2_un, const float* b2, float* out, int32_t* arg,
+                            void* m0, void* m1, int B, int N1, int M, void* stream);
+/* The level's backward in the order of geoa3_pn2ssg_backward: sa2b_prep_kernel, sa2b_bwd_kernel, affine3_grad_pm_kernel
+ * (dnx1 = W_x^T dr), sa2b_centre_kernel (dnx2 -= the centres' share: dnx2 holds the caller's values on entry).  The sizes are
+ * the classifier's: 128 centres, 64 samples, 512 points.  dout / out / arg [B][256][128], gidx [B][128][64] (indices in [0, 512);
+ * arg in [0, 64) and below the ball's count of distinct points), m1 / m0 the forward's gate words, W2 [256][128], w1t_img /
+ * w1t_un the fragment image of W1^T, Wx [128][3]; dr [B][512][128], dnx1 [B][512][3], dnx2 [B][128][3].
+ * scratch: geoa3_debug_pn2_sa2b_scratch_bytes(B) bytes, 256-byte aligned; it stays readable afterwards.  Per cloud
+ * (geoa3_debug_pn2_sa2b_scratch_bytes(1) bytes each), in this order, R = the cloud's hit rows (a row = (centre, sample) some
+ * live pooled channel points at; live: out > 0 and dout != 0), in (destination point, centre) order:
+ *   int32 [8192]   row keys: dest | sample << 9 | centre << 15 | last-of-dest << 31                        (R written)
+ *   int32 [32768]  entries, row by row, ascending channel: channel | column << 16 | last-of-row << 31, column = the row's
+ *                  position in its part, mod 64                                                            (the live channels)
+ *   float [32768]  the entries' gradients
+ *   int4  [132]    tiles of up to 64 rows: row0, rows, entry0, entries | (entries of rows 0-31) << 16
+ *   int32 [8]      tile prefix of the 4 parts ([0..4] written); parts are cut where a destination starts: part q begins at
+ *                  the first destination whose first row is at or behind floor(R q / 4)
+ *   u64   [128]    bit s of word m = (centre m, sample s) is a hit row
+ *   float [128][64][3]  W_x^T d a0 of each hit row, at [centre][sample]
+ * rounded up to a multiple of 256 bytes. */
+int64_t geoa3_debug_pn2_sa2b_scratch_bytes(int B);
+int geoa3_debug_pn2_sa2b(const float* dout, const float* out, const int32_t* arg, const int32_t* gidx, const void* m1,
+                         const void* m0, const float* W2, const void* w1t_img, const float* w1t_un, const float* Wx,
+                         void* scratch, float* dr, float* dnx1, float* dnx2, int B, void* stream);
+/* Names and byte offsets (address order) of the buffers geoa3_pn2ssg_forward / _backward keep in their workspace, one per
+ * field of the workspace, then "end" = geoa3_pn2ssg_workspace_bytes(B, N).  Returns the number of names, -1 for sizes the
+ * native path refuses.  Some buffers serve twice: the forward keeps rT (the pre-transformed rows) in `df1` and, with a side
+ * queue, the sampler's running distances in `d1`; the backward writes dr over `r` and, with a side queue, the scattered
+ * centroid gradient gx2 over `f1`. */
+int geoa3_debug_pn2ssg_workspace_layout(int B, int N, const char** names, int64_t* offsets, int cap);
+
 #ifdef __cplusplus
 }
 #endif
