@@ -175,6 +175,7 @@ SIGNATURES = {
     "geoa3_debug_pn2_sa2_fwd": (C.c_int, [vp] * 13 + [C.c_int, C.c_int, C.c_int, vp]),
     "geoa3_debug_pn2_sa2b_scratch_bytes": (C.c_int64, [C.c_int]),
     "geoa3_debug_pn2_sa2b": (C.c_int, [vp] * 14 + [C.c_int, vp]),
+    "geoa3_debug_pn2_sa1_scatter": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_debug_pn2ssg_workspace_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
                                                       C.c_int]),
     "geoa3_profile_enable": (C.c_int, [C.c_int]),

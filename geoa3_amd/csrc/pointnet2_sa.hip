@@ -491,6 +491,12 @@ __global__ __launch_bounds__(SA_T) __attribute__((amdgpu_waves_per_eu(SA_WB / 4,
   // d h2 = W3^T dz3 with |dz3| 2^kg < 2^14: the accumulators (2^(k3 + kg) d h2) stay below 2^(k3 + EW3T + 14), so the
   // operand scale of the next product is the same for every centroid
   const int kd = -k3 - EW3T;
+  // The pooled gradient's own scale 2^kg comes from its measured maximum, kg = 140 - E.  How small a maximum it follows is set
+  // by the format alone: 2^kg must be a float (kg <= 127: E >= 13), and so must the unscale factor of the result, f1 =
+  // 2^-(k2 + kd + k3 + kg) = 2^-(k2 - EW3T + kg) (k2 - EW3T + 140 - E <= 126: E >= 14 + k2 - EW3T).  A centroid whose largest
+  // gradient lies below 2^(kg_lo - 127) -- about 2^-100 -- cannot be scaled: its results are NaN (f1 as a bit pattern: this
+  // file is compiled with -fno-honor-nans), never the zeros a clamped scale would silently return.
+  const int kg_lo0 = 14 + k2 - EW3T, kg_lo = kg_lo0 < 13 ? 13 : kg_lo0;
   // one-hot records of the wave's centroid: channel PAIRS (2 q, 2 q + 1) as packed fp16 images of the scaled pooled gradient
   // (hi pieces | lo pieces), and per channel the arg-max sample as a one-hot bit over samples 0-31 | 32-63
   unsigned* s_hp = L.pa + wave * 384;   // [64]
@@ -504,6 +510,7 @@ __global__ __launch_bounds__(SA_T) __attribute__((amdgpu_waves_per_eu(SA_WB / 4,
     asm volatile("" ::: "memory");   // the weights stay in LDS: no hoisting of their loads out of the centroid loop
     const Sa1Pts Q = P;
     int kg;
+    bool unscalable;   // (wave-uniform)
     {
       // every channel's scaled gradient (through the output relu) is split ONCE by the lane that loads it; the one-hot
       // operand construction below is then a bit-field extract per channel (0 / -1: is this lane's sample the channel's
@@ -513,7 +520,10 @@ __global__ __launch_bounds__(SA_T) __attribute__((amdgpu_waves_per_eu(SA_WB / 4,
       const float2 gv = *reinterpret_cast<const float2*>(g + (size_t)c * 128 + 2 * lane);
       const unsigned av = *reinterpret_cast<const unsigned short*>(arg + (size_t)c * 128 + 2 * lane);
       const float g0 = ov.x > 0.f ? gv.x : 0.f, g1 = ov.y > 0.f ? gv.y : 0.f;
-      kg = sa_k(wave_max(fmaxf(__builtin_fabsf(g0), __builtin_fabsf(g1))));
+      const float gm = wave_max(fmaxf(__builtin_fabsf(g0), __builtin_fabsf(g1)));
+      kg = sa_k(gm, kg_lo);
+      const unsigned gb = __float_as_uint(gm) & 0x7fffffffu;
+      unscalable = gb != 0u && (int)(gb >> 23) < kg_lo;
       const float sg = sa_pow2(kg);
       const float z0 = g0 * sg, z1 = g1 * sg;
       _Float16 h0, l0, h1, l1;
@@ -655,7 +665,7 @@ __global__ __launch_bounds__(SA_T) __attribute__((amdgpu_waves_per_eu(SA_WB / 4,
               sz = __builtin_fmaf(wr3[3 * i + 2], v, sz);
             }
           }
-        const float f1 = sa_pow2(-(k2 + kd + k3 + kg));
+        const float f1 = unscalable ? __uint_as_float(0x7fc00000u) : sa_pow2(-(k2 + kd + k3 + kg));
         sx = (sx + __shfl_xor(sx, 32, 64)) * f1;
         sy = (sy + __shfl_xor(sy, 32, 64)) * f1;
         sz = (sz + __shfl_xor(sz, 32, 64)) * f1;
@@ -795,6 +805,27 @@ extern "C" int64_t geoa3_pn2_sa1_scratch_bytes(int B, int M) {
   return (int64_t)B * M * SA_S * 3 * (int64_t)sizeof(float);
 }
 
+// sa1_scatter_kernel keeps one instance's sums in LDS: 3 N 64-bit accumulators, the reduction scratch, a bit per point
+static size_t sa1_scatter_lds(int N) {
+  return (size_t)3 * N * sizeof(unsigned long long) + 16 * sizeof(float) + ((size_t)(N + 31) / 32) * sizeof(unsigned);
+}
+static bool sa1_scatter_fits(int N) { return sa1_scatter_lds(N) <= 160 * 1024 - 512; }   // (N <= ~6800 points)
+static void launch_sa1_scatter(const float* dp, const int32_t* idx, int B, int N, int M, float* dxyz, hipStream_t s) {
+  const size_t l2 = sa1_scatter_lds(N);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa1_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)l2);
+  hipLaunchKernelGGL(sa1_scatter_kernel, dim3(B), dim3(SCAT_BLOCK), l2, s, dp, idx, dxyz, N, M);
+}
+
+// sa1_scatter_kernel alone (include/geoa3_hip_debug.h): dp [B][M][64][3] as geoa3_pn2_sa1_backward leaves it in its scratch
+extern "C" int geoa3_debug_pn2_sa1_scatter(const float* dp, const int32_t* idx, int B, int N, int M, float* dxyz, void* stream) {
+  if (!dp || !idx || !dxyz || B <= 0 || N <= 0 || M <= 0) return GEOA3_EINVAL;
+  if ((long)B * M > (1L << 24) || !sa1_scatter_fits(N)) return GEOA3_ENOSUPPORT;
+  launch_sa1_scatter(dp, idx, B, N, M, dxyz, geoa3_stream(stream));
+  GEOA3_CHECK_LAUNCH();
+  return GEOA3_OK;
+}
+
 // (after_bwd: recorded behind sa1_bwd_kernel, in front of the scatter -- grad_new_xyz is complete there)
 int launch_sa1_backward(const float* xyz, const float* new_xyz, const int32_t* idx, const geoa3_sa1_weights* w, int B, int N, int M,
                         const float* out, const uint8_t* arg, const float* grad_out, float* grad_xyz, float* grad_new_xyz,
@@ -816,8 +847,7 @@ int launch_sa1_backward(const float* xyz, const float* new_xyz, const int32_t* i
   if ((long)B * M > (1L << 24)) return GEOA3_ENOSUPPORT;
   hipStream_t s = geoa3_stream(stream);
   // deterministic scatter (scratch given and the owner's accumulators + at least one centroid's lists fit LDS)
-  const size_t l2 = (size_t)3 * N * sizeof(unsigned long long) + 16 * sizeof(float) + ((size_t)(N + 31) / 32) * sizeof(unsigned);
-  const bool det = scratch && l2 <= 160 * 1024 - 512;     // (N <= ~6800 points: the sums of one instance in LDS)
+  const bool det = scratch && sa1_scatter_fits(N);     // (N <= ~6800 points: the sums of one instance in LDS)
   if (!det && hipMemsetAsync(grad_xyz, 0, (size_t)B * N * 3 * sizeof(float), s) != hipSuccess) return GEOA3_ELAUNCH;
   const size_t lds = (size_t)sa1_lds_bytes(SA_WB, true);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa1_bwd_kernel<SA_WB * 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -827,11 +857,7 @@ int launch_sa1_backward(const float* xyz, const float* new_xyz, const int32_t* i
                      grad_out, grad_xyz, grad_new_xyz, det ? scratch : nullptr);
   geoa3_prof_end(GEOA3_PROF_SA1_BWD, s);
   if (after_bwd && hipEventRecord(after_bwd, s) != hipSuccess) return GEOA3_ELAUNCH;
-  if (det) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sa1_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)l2);
-    hipLaunchKernelGGL(sa1_scatter_kernel, dim3(B), dim3(SCAT_BLOCK), l2, s, scratch, idx, grad_xyz, N, M);
-  }
+  if (det) launch_sa1_scatter(scratch, idx, B, N, M, grad_xyz, s);
   GEOA3_CHECK_LAUNCH();
   return GEOA3_OK;
 }

@@ -175,6 +175,15 @@ int64_t geoa3_debug_pn2_sa2b_scratch_bytes(int B);
 int geoa3_debug_pn2_sa2b(const float* dout, const float* out, const int32_t* arg, const int32_t* gidx, const void* m1,
                          const void* m0, const float* W2, const void* w1t_img, const float* w1t_un, const float* Wx,
                          void* scratch, float* dr, float* dnx1, float* dnx2, int B, void* stream);
+/* Level 1's backward needs no entry of its own: geoa3_pn2_sa1_backward (geoa3_hip.h) already takes out, arg and grad_out, and
+ * with a scratch buffer (deterministic mode: N small enough for one instance's sums in LDS) it leaves dp [B][M][64][3] readable
+ * in scratch afterwards -- the gradient of every (centroid, sample) difference, a ball's padded samples (repeats of its first
+ * index) merged into sample 0 and zero themselves.  This entry is the second kernel of that mode alone (sa1_scatter_kernel):
+ * dxyz [B][N][3] = the sum of dp over the (centroid, sample) whose idx [B][M][64] names the point, padded samples skipped, as
+ * an order-free 64-bit fixed-point sum at 2^(Ex - 40), 2^Ex the power of two above the instance's largest finite |dp|
+ * (Ex clamped to [-80, 80]); a NaN / infinite entry makes its destination NaN, an infinite maximum the whole instance.
+ * Every index must lie in [0, N).  GEOA3_ENOSUPPORT when N is beyond what geoa3_pn2_sa1_backward takes in that mode. */
+int geoa3_debug_pn2_sa1_scatter(const float* dp, const int32_t* idx, int B, int N, int M, float* dxyz, void* stream);
 /* Names and byte offsets (address order) of the buffers geoa3_pn2ssg_forward / _backward keep in their workspace, one per
  * field of the workspace, then "end" = geoa3_pn2ssg_workspace_bytes(B, N).  Returns the number of names, -1 for sizes the
  * native path refuses.  Some buffers serve twice: the forward keeps rT (the pre-transformed rows) in `df1` and, with a side

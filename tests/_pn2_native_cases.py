@@ -267,3 +267,137 @@ def sa2b_reference(c, rows=None, **defects):
     r = R.sa2_bwd(sel(c["dout"]).double(), sel(c["out"]).double(), sel(c["arg"]), sel(c["gidx"]), sel(c["gate0"]),
                   sel(c["gate1"]), c["W1"].double(), c["W2"].double(), c["Wx"].double(), sel(c["dnx2_in"]).double(), **defects)
     return r, R.sa2_bwd_tolerances(r)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sa1 backward: sa1_bwd_kernel + sa1_scatter_kernel (64 samples; any B, M, N)
+# ---------------------------------------------------------------------------------------------------------------------
+# (B, M, N): 3 centroids = fewer than the 8 wavefronts of a workgroup; 3 x 40 on 300 points = the real ball query at radius
+# 0.25 with a duplicated point; 5 x 512 = 2560 centroids, just over the 2048 the grid's 256 workgroups of 8 wavefronts take in
+# one pass: 512 wavefronts take a second centroid through the prefetch.
+SA1B_SHAPES = [(1, 3, 40), (3, 40, 300), (5, 512, 128)]
+# variants of a shape (the same seed: a variant is the random case with the named change)
+#   padding      centroid 0 a ball of ONE real point (63 repeats), centroid 1 a FULL ball, centroid 2 a ball whose repeats
+#                begin at sample 32 (the column-block boundary)
+#   padding_arg  padding, with arg naming a REPEAT of sample 0 for some channels whose maximum sits at sample 0
+#   zeros        centroid 1 with every out <= 0, centroid 2 with g == 0
+#   band         b1 and b2 nudged so that one z1 and one z2 of a row that carries gradient sit inside their bands
+#   g_channel    one channel's g 2^12 times the rest;     g_centroid   one centroid's g 2^20 times its workgroup neighbours
+#   w1_small / w1_big   max|W1| = 2^-6 / 2^6 max|b1|;     coincide     a ball whose points all coincide with the centroid
+SA1B_STRESS = ["g_channel", "g_centroid", "w1_small", "w1_big", "coincide"]
+# the ball query's radius: 0.25, but 0.6 for the 2560 centroids -- mostly full balls, where half the rows are nobody's arg-max
+# and carry neither gradient nor allowance (at 0.25 every row of a ball of ~8 points does, and ~1.5e-3 of them have one of
+# their 128 gates in its band: over the cap however the case is seeded)
+SA1B_RADIUS = {(5, 512, 128): 0.6}
+SA1B_BAND = (2, 40, 300, "band")      # (about 1200 non-padded rows: the cap admits the ONE row the case puts into its bands)
+SA1B_SHARE = 1e-3          # at most this part of a case's non-padded dp rows may carry an allowance (the share 8b uses for m1)
+
+
+def _sa1_fwd64(c, b, layers=None):
+    L = layers if layers is not None else c["layers"]
+    return R.sa1_fwd(c["xyz"][b], c["nx"][b], c["gidx"][b], [(w.double(), v.double()) for w, v in L])
+
+
+@functools.lru_cache(maxsize=None)
+def sa1b_case(B, M, N, variant="random"):
+    """-> dict B, M, N, xyz [B][N][3], nx [B][M][3], gidx [B][M][64] int32, layers = ((W1, b1), (W2, b2), (W3, b3)) float32, out
+    [B][M][128] float32 and arg [B][M][128] uint8 from the FLOAT64 forward restatement (the backward is tested apart from the
+    forward kernel), g [B][M][128]; band: the nudged (layer, cloud, m, s, channel) gates of the variant of that name."""
+    from oracle import pointnet2_oracle as O
+    g = torch.Generator().manual_seed(6000 + B + M + N)
+    xyz = torch.rand(B, N, 3, generator=g) - 0.5
+    xyz[:, 7] = xyz[:, 3]                                          # a duplicated point
+    nx = xyz[:, (torch.arange(M) * 7) % N].clone()
+    if M > N:                                                      # more centroids than points: given directly, no sampler
+        nx[:, N:] += 0.02 * torch.randn(B, M - N, 3, generator=g)
+    gidx = O.ball_query(nx.contiguous(), xyz, SA1B_RADIUS.get((B, M, N), 0.25), 64).clone()
+    layers = [[torch.randn(co, ci, generator=g) * (2.0 / ci) ** 0.5, torch.randn(co, generator=g) * 0.1]
+              for ci, co in ((3, 64), (64, 64), (64, 128))]
+    grad = torch.randn(B, M, 128, generator=g)
+    if variant in ("padding", "padding_arg"):
+        assert M >= 3 and N >= 64
+        gidx[0, 0, :] = gidx[0, 0, 0]
+        gidx[0, 1, :] = torch.arange(64, dtype=torch.int32)
+        gidx[0, 2, :32] = torch.arange(8, 40, dtype=torch.int32)
+        gidx[0, 2, 32:] = 8
+    elif variant == "g_channel":
+        grad[:, :, 5] *= 2.0 ** 12
+    elif variant == "g_centroid":
+        grad[:, 1] *= 2.0 ** 20
+    elif variant in ("w1_small", "w1_big"):
+        want = 2.0 ** (-6 if variant == "w1_small" else 6)
+        layers[0][0] *= want * float(layers[0][1].abs().max()) / float(layers[0][0].abs().max())
+    elif variant == "coincide":
+        gidx[:, 0, :] = 11
+        nx[:, 0] = xyz[:, 11]
+    c = dict(B=B, M=M, N=N, xyz=xyz.contiguous(), nx=nx.contiguous(), gidx=gidx.contiguous(), g=grad, band=[])
+    if variant == "band":
+        # a row that carries gradient: the arg-max sample of channel 0 at centroid 1 of cloud 0.  First b1 (z2 depends on it),
+        # then b2: the nudged z is what float32 rounding of the bias leaves, far inside tol(z).
+        f = _sa1_fwd64(c, 0, layers)
+        m, s = 1, int(f["arg"][1, 0])
+        layers[0][1][9] -= float(f["z1"][m, s, 9])
+        f = _sa1_fwd64(c, 0, layers)
+        s = int(f["arg"][1, 0])
+        layers[1][1][21] -= float(f["z2"][m, s, 21])
+        f = _sa1_fwd64(c, 0, layers)
+        s2 = int(f["arg"][1, 0])
+        c["band"] = [(1, 0, m, s, 9), (2, 0, m, s, 21)] if s2 == s else []
+    c["layers"] = tuple((w.contiguous(), v.contiguous()) for w, v in layers)
+    fw = [_sa1_fwd64(c, b) for b in range(B)]
+    c["out"] = torch.stack([f["out"].float() for f in fw]).contiguous()
+    arg = torch.stack([f["arg"] for f in fw])
+    if variant in ("padding", "padding_arg"):
+        # (the backward routes a channel's gradient to whatever sample arg names: every fourth channel of centroid 2 is SENT to
+        # sample 0, so that the ball with real points and repeats has channels there)
+        arg[0, 2, 0::4] = 0
+    if variant == "padding_arg":
+        assert int(arg[0, 0].max()) == 0
+        arg[0, 0, 0::3], arg[0, 0, 1::3] = 63, 33
+        at0 = arg[0, 2] == 0
+        arg[0, 2][at0] = 40
+        c["renamed"] = int(at0.sum())
+    elif variant == "zeros":
+        c["out"][0, 1, 0::2], c["out"][0, 1, 1::2] = 0.0, -1.0
+        grad[0, 2] = 0.0
+    c["arg"] = arg.to(torch.uint8).contiguous()
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def sa1b_reference(B, M, N, variant="random"):
+    """the float64 restatement of every cloud of the case: a list of R.sa1_bwd results"""
+    c = sa1b_case(B, M, N, variant)
+    L64 = [(w.double(), v.double()) for w, v in c["layers"]]
+    return [R.sa1_bwd(c["xyz"][b], c["nx"][b], c["gidx"][b], L64, c["out"][b], c["arg"][b], c["g"][b]) for b in range(B)]
+
+
+def sa1b_checks(refs, dp, dnew, dxyz, what, allowance=True):
+    """dp [B][M][64][3], dnew [B][M][3], dxyz [B][N][3] (CPU) held to bound + allowance, cloud by cloud; padded rows of dp
+    exactly zero; dp None (the float-atomic form writes none): the other two.  -> {name: worst err / tol}.  Raises
+    AssertionError."""
+    worst = {"dnew": 0.0, "dxyz": 0.0} if dp is None else {"dp": 0.0, "dnew": 0.0, "dxyz": 0.0}
+    for b, r in enumerate(refs):
+        assert dp is None or not bool(dp[b][r["pad"]].any()), "%s: a padded row of dp is not zero" % what
+        for name, got in (("dp", dp), ("dnew", dnew), ("dxyz", dxyz)):
+            if got is None:
+                continue
+            got = got[b]
+            ref, _, tol, allow = r[name]
+            worst[name] = max(worst[name], R.worst_ratio(got, ref, tol + allow if allowance else tol))
+    print("worst err/tol %-44s " % what + " ".join("%s %.4f" % kv for kv in worst.items()))
+    assert max(worst.values()) <= 1.0, (what, worst)
+    return worst
+
+
+def sa1b_share(refs):
+    """the part of a case's non-padded dp rows that carries an allowance"""
+    return sum(r["share"][0] for r in refs) / max(1, sum(r["share"][1] for r in refs))
+
+
+def sa1b_emulate(c, **kw):
+    """the CPU emulation of the kernels' arithmetic on every cloud of a case -> dp [B][M][64][3], dnew, dxyz"""
+    outs = [R.sa1_bwd_split(c["xyz"][b], c["nx"][b], c["gidx"][b], c["layers"], c["out"][b], c["arg"][b], c["g"][b],
+                            flip=[f[:1] + f[2:] for f in kw.get("flip", ()) if f[1] == b],
+                            **{k: v for k, v in kw.items() if k != "flip"}) for b in range(c["B"])]
+    return tuple(torch.stack([o[i] for o in outs]) for i in range(3))

@@ -460,7 +460,7 @@ def affine3_add(Y, Wx, bias, p, relu):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# sa1_fwd_kernel: level 1's forward (the backward recomputes its gates in the kernel and is not restated: DESIGN 8b)
+# sa1_fwd_kernel: level 1's forward (its z1, z2 and their tolerances are also the gates and bands of sa1_bwd below)
 # ---------------------------------------------------------------------------------------------------------------------
 def sa1_fwd(xyz, nx, gidx, layers, skip_k2=None):
     """ONE cloud: xyz [N][3], nx [M][3] centroids, gidx [M][64], layers = ((W1 [64][3], b1), (W2 [64][64], b2), (W3 [128][64], b3)):
@@ -468,7 +468,8 @@ def sa1_fwd(xyz, nx, gidx, layers, skip_k2=None):
     dtype of the weights z1 = W1 d + b1, z2 = W2 relu(z1) + b2, y3 = W3 relu(z2) + b3, out = relu(max_s y3).
     -> dict out [M][128], y3 [M][64][128], arg (first maximal sample), tol_y3, tol_out: every layer is a split-fp16 product, so
     as for level 2 tol(z1) = bound(z1, 3 + 1 terms), tol(z2) = bound(z2, 64 + 1) + |W2| tol(z1), tol(y3) = bound(y3, 64 + 1) +
-    |W3| tol(z2), tol(out) = max_s tol(y3).  skip_k2: that k left out of the second product."""
+    |W3| tol(z2), tol(out) = max_s tol(y3); also z1, z2 [M][64][64] and t1, t2 = tol(z1), tol(z2).  skip_k2: that k left out of
+    the second product."""
     (W1, b1), (W2, b2), (W3, b3) = layers
     dt = W1.dtype
     M = nx.shape[0]
@@ -485,7 +486,265 @@ def sa1_fwd(xyz, nx, gidx, layers, skip_k2=None):
     t3 = tolerance(y3, m3, 65, extra=SPLIT) + t2 @ W3.abs().t()
     top = y3.max(1, keepdim=True).values
     return dict(out=top.squeeze(1).clamp_min(0), y3=y3, arg=(y3 == top).to(torch.uint8).argmax(1), tol_y3=t3,
-                tol_out=t3.max(1).values)
+                tol_out=t3.max(1).values, z1=z1, z2=z2, t1=t1, t2=t2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sa1_bwd_kernel + sa1_scatter_kernel: level 1's backward.  The kernel recomputes z1 and z2 and takes its relu gates from
+# THEIR signs, so a gate whose |z| lies inside tol(z) may differ from the float64 sign: sa1_bwd returns, beside (value, mag,
+# tol), an ALLOWANCE per entry = what the in-band gates behind that entry toggle, to first order.
+# ---------------------------------------------------------------------------------------------------------------------
+def biased_exponent(m) -> int:
+    return (int(np.float32(m).view(np.uint32)) >> 23) & 0xFF
+
+
+def l1_exponent(x) -> int:
+    """E with x < 2^E, from the float32 exponent field, at least -100 (sa1_stage's kw[3..8])"""
+    return max(biased_exponent(x) - 126, -100)
+
+
+def pad_mask(gidx):
+    """bool [M][64]: samples that repeat the row's first index (the ball query's padding)"""
+    pad = gidx == gidx[:, :1]
+    pad[:, 0] = False
+    return pad
+
+
+def merge_padding(v, pad):
+    """v [M][64][3]: the padded samples' rows added into sample 0 and zeroed"""
+    p = pad.unsqueeze(-1).to(v.dtype)
+    out = v * (1 - p)
+    out[:, 0] = out[:, 0] + (v * p).sum(1)
+    return out
+
+
+def sa1_bwd(xyz, nx, gidx, layers, out, arg, g, lose=None):
+    """ONE cloud, inputs as sa1_fwd plus out [M][128] (the pooled output: a channel is live where out > 0), arg [M][128] (the
+    sample the channel's maximum sits at) and g [M][128] (the upstream gradient):
+        dz3[s][ch] = g[ch] [out[ch] > 0] [arg[ch] == s]     dh2 = W3^T dz3      dz2 = dh2 [z2 > 0]
+        dh1 = W2^T dz2      dz1 = dh1 [z1 > 0]      dp = W1^T dz1 per (centroid, sample), then the padded samples merged into
+        sample 0;      dnew = -sum_s dp;      dxyz = the scatter of dp by gidx.
+    -> dict: dp, dnew, dxyz = (value, mag, tol, allowance); pad; share = (the non-padded rows of dp with a non-zero allowance,
+    the non-padded rows); Ex = the scatter's exponent (2^Ex above the largest |dp|).
+    tol composes like sa1_fwd's: each product's own bound (128 / 64 / 64 terms; + SPLIT for the two split products) + the
+    tolerance of its operand through the absolute weights and the gates that are open OR in band, + the operand floors
+    (tests/test_gpu_pn2_sa1_bwd.py), computed from the centroid's largest live |g| WITHOUT the kernel's clamp: the reference and
+    its bound are scale-free.  lose = (what, index): one term left out of the value (never of mag) --
+    ("ch", (m, s, ch)), ("k2", j), ("row", i), ("sample", (m, s)), ("dup", (m, s)), ("entry", (m, s))."""
+    (W1, b1), (W2, b2), (W3, b3) = layers
+    dt = W1.dtype
+    what, where = lose if lose is not None else (None, None)
+    f = sa1_fwd(xyz, nx, gidx, layers)
+    z1, z2, t1, t2 = f["z1"], f["z2"], f["t1"], f["t2"]
+    M, N = nx.shape[0], xyz.shape[0]
+    g0 = torch.where(out > 0, g, torch.zeros_like(g)).to(dt)
+    onehot = arg.long().unsqueeze(1) == torch.arange(64).view(1, 64, 1)                    # [M][64][128]
+    A = onehot.to(dt) * g0.unsqueeze(1)
+    Av = A
+    if what == "ch":
+        Av = A.clone()
+        Av[where] = 0
+    # the operand floors: an element scaled by 2^k whose lo piece is an fp16 subnormal is carried to 2^-25 (half the subnormal
+    # step 2^-24) there, 2^(-25 - k) unscaled.  dz3 rides at kg = 140 - E(max |g0|); dz2 at kg - EW3T (the accumulators hold
+    # 2^(k3 + kg) dh2 and are scaled by 2^kd, kd = -k3 - EW3T, 2^EW3T above the largest column l1 norm of W3).
+    gmax = g0.abs().max(1).values.float()
+    fg = torch.tensor([2.0 ** (biased_exponent(v) - 165) if v > 0 else 0.0 for v in gmax.tolist()], dtype=dt).view(M, 1, 1)
+    EW3T = l1_exponent(W3.float().abs().sum(0).max())
+    fd = fg * 2.0 ** EW3T
+    dh2, mag2 = Av @ W3, A.abs() @ W3.abs()
+    tol2 = tolerance(dh2, mag2, 128, extra=SPLIT) + ((A != 0).to(dt) * fg) @ W3.abs()
+    open2, band2 = z2 > 0, z2.abs() <= t2
+    ok2 = (open2 | band2).to(dt)
+    dz2 = dh2 * open2
+    if what == "k2":
+        dz2 = dz2.clone()
+        dz2[..., where] = 0
+    dh1, mag1 = dz2 @ W2, (mag2 * open2) @ W2.abs()
+    tol1 = tolerance(dh1, mag1, 64, extra=SPLIT) + ((tol2 + fd * (mag2 > 0)) * ok2) @ W2.abs()
+    open1, band1 = z1 > 0, z1.abs() <= t1
+    ok1 = (open1 | band1).to(dt)
+    dz1 = dh1 * open1
+    if what == "row":
+        dz1 = dz1.clone()
+        dz1[..., where] = 0
+    dp, magp = dz1 @ W1, (mag1 * open1) @ W1.abs()
+    tolp = tolerance(dp, magp, 64) + (tol1 * ok1) @ W1.abs()
+    # what the in-band gates toggle: a z2 gate j moves dz2[j] by |dh2[j]|, through |W2[j, :]|, the z1 gates that are open or in
+    # band themselves (the cross term) and |W1|; a z1 gate i moves dz1[i] by |dh1[i]|, through |W1[i, :]|
+    allow = ((((dh2.abs() * band2) @ W2.abs()) * ok1) + dh1.abs() * band1) @ W1.abs()
+    pad = pad_mask(gidx)
+    npad = pad.sum(1)
+    dnew_v = dp
+    if what == "sample":
+        dnew_v = dp.clone()
+        dnew_v[where] = 0
+    dnew, mnew = -dnew_v.sum(1), magp.sum(1)
+    tnew = tolp.sum(1) + tolerance(dnew, mnew, 64)
+    dpv = dp
+    if what == "dup":
+        assert bool(pad[where])
+        dpv = dp.clone()
+        dpv[where] = 0
+    dpm, magm, allowm = merge_padding(dpv, pad), merge_padding(magp, pad), merge_padding(allow, pad)
+    tolm = merge_padding(tolp, pad)
+    tolm[:, 0] = tolm[:, 0] + (npad > 0).to(dt).view(M, 1) * tolerance(torch.zeros_like(magm[:, 0]), magm[:, 0], 64)
+    keep = ~pad
+    if what == "entry":
+        assert bool(keep[where])
+        keep = keep.clone()
+        keep[where] = False
+    dest = gidx.long()[~pad]
+    sc = lambda v, sel: torch.zeros(N, 3, dtype=dt).index_add_(0, gidx.long()[sel], v[sel])
+    dxyz, magx, allowx, carried = sc(dpm, keep), sc(magm, ~pad), sc(allowm, ~pad), sc(tolm, ~pad)
+    cnt = torch.bincount(dest, minlength=N).to(dt).view(N, 1)
+    top = float(dpm.abs().max())
+    Ex = min(max(biased_exponent(top) - 126, -80), 80)
+    # the fixed-point scatter rounds every contribution to 2^(Ex' - 40), Ex' the exponent of the KERNEL's largest |dp|: within
+    # its tolerance of the reference's, so at most one binade above; the float atomics (no scratch) are a plain fp32 sum
+    tolx = carried + torch.maximum(cnt * 2.0 ** (Ex + 1 - 41) + 2.0 ** -24 * dxyz.abs(), tolerance(dxyz, magx, max(int(cnt.max()), 1)))
+    live = ~pad
+    share = (int((allowm[live] > 0).any(-1).sum()), int(live.sum()))
+    return dict(dp=(dpm, magm, tolm, allowm), dnew=(dnew, mnew, tnew, allow.sum(1)), dxyz=(dxyz, magx, tolx, allowx), pad=pad,
+                share=share, Ex=Ex)
+
+
+def sa1_scatter_fixed(dp32, gidx, N):
+    """sa1_scatter_kernel bit for bit, ONE instance: dp32 float32 [M][64][3], gidx [M][64] -> float32 numpy [N][3].  The largest
+    finite magnitude of ALL entries by bit pattern (NaNs skipped) -> Ex = its exponent field - 126, clamped to [-80, 80]; every
+    non-padded, finite contribution x -> round-half-even(x 2^(40 - Ex)) as a 64-bit integer (saturating); the integer sum per
+    destination (wrapping); one rounding to float32, times 2^(Ex - 40).  A row with a NaN / infinite component makes its
+    destination NaN; an infinite maximum makes every destination NaN."""
+    d = np.ascontiguousarray(np.asarray(dp32, dtype=np.float32)).reshape(-1, 3)
+    idx = np.asarray(gidx).astype(np.int64).reshape(-1, 64)
+    bits = d.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    ok = bits <= 0x7F800000
+    m = int(bits[ok].max()) if ok.any() else 0
+    finite = m < 0x7F800000
+    Ex = min(max(((m >> 23) & 0xFF) - 126, -80), 80)
+    pad = idx == idx[:, :1]
+    pad[:, 0] = False
+    keep = ~pad.reshape(-1)
+    dest = idx.reshape(-1)[keep]
+    rows, rbits = d[keep], bits[keep]
+    bad_row = (rbits >= 0x7F800000).any(1)
+    bad = np.zeros(N, dtype=bool)
+    bad[dest[bad_row]] = True
+    with np.errstate(over="ignore", invalid="ignore"):
+        scaled = np.float32(2.0 ** (40 - Ex)) * rows[~bad_row]                      # (float32: exact, a power of two)
+    q = np.clip(np.rint(scaled.astype(np.float64)), -2.0 ** 63, 2.0 ** 63 - 1024)
+    qi = np.where(q >= 2.0 ** 63 - 1024, np.int64(2 ** 63 - 1), q.astype(np.int64))
+    acc = np.zeros((N, 3), dtype=np.int64)
+    with np.errstate(over="ignore"):
+        np.add.at(acc, dest[~bad_row], qi)
+    out = acc.astype(np.float32) * np.float32(2.0 ** (Ex - 40))
+    if not finite:
+        bad[:] = True
+    out[bad] = np.float32("nan")
+    return out
+
+
+def sa1_scatter_bound(dp32, gidx, N):
+    """-> (float64 sum [N][3], bound [N][3], Ex) of one finite instance: cnt 2^(Ex - 41) + 2^-24 |sum|, cnt = the entries landing
+    at the destination (each rounded to half a step of 2^(Ex - 40); one float32 rounding of the sum)"""
+    d = torch.as_tensor(np.asarray(dp32, dtype=np.float32)).double().reshape(-1, 64, 3)
+    idx = torch.as_tensor(np.asarray(gidx)).long().reshape(-1, 64)
+    keep = ~pad_mask(idx)
+    ref = torch.zeros(N, 3, dtype=torch.float64).index_add_(0, idx[keep], d[keep])
+    cnt = torch.bincount(idx[keep], minlength=N).double().view(N, 1)
+    Ex = min(max(biased_exponent(float(d.abs().max())) - 126, -80), 80)
+    return ref, cnt * 2.0 ** (Ex - 41) + 2.0 ** -24 * ref.abs(), Ex
+
+
+def sa_k(m, lo=110, hi=254) -> int:
+    """the kernels' scale rule of pointnet2_sa.hip: k with m 2^k in [2^13, 2^14), the exponent field clamped to [lo, hi]"""
+    return 140 - min(max(biased_exponent(m), lo), hi)
+
+
+def sa_perm(p):
+    """channel held at position p of a k-permuted image (the 32x32 accumulator's row order)"""
+    ks, h, j = p >> 4, (p >> 3) & 1, p & 7
+    return 32 * (ks >> 1) + 16 * (ks & 1) + 4 * h + (j & 3) + 8 * (j >> 2)
+
+
+def sa1_bwd_split(xyz, nx, gidx, layers, out, arg, g, defect=None, flip=(), kg_lo=None):
+    """sa1_bwd in the kernels' arithmetic for ONE cloud -> (dp merged, dnew, dxyz) float32: per centroid the differences at
+    2^kp split, layer 1 as one product with hi and lo pieces of both sides (bias against 2^kp), h1 at the scale kx the l1 bounds
+    give, layer 2 with its bias as the accumulators' initial value; the gates are the signs of THESE accumulators; the live
+    gradient at 2^kg one-hot against the W3^T image, the gated result at 2^kd against the W2^T image, the gated result against
+    W1 in float32; then the merge, the float32 sums and the fixed-point scatter.
+    defect: "no_ex" (the merged duplicates left out of sample 0), "mask_block0" (samples 32-63 read the one-hot mask of samples
+    0-31), "skip_ks3" / "skip_ks2" (the last k-step of the W3^T / W2^T product lost), "no_hcb" (every lane keeps the second column
+    block's result).  flip: (layer, m, s, channel) gates inverted.  kg_lo: the lowest exponent field the gradient's scale
+    follows -- None: the kernel's, max(14 + k2 - EW3T, 13), below which a centroid with gradient comes out as NaN; 110:
+    the kernel as it was, which kept the scale 2^30 below 2^-17 and returned what was left (in the end zeros)."""
+    f32 = np.float32
+    F = lambda t: t.astype(f32)
+    p2 = lambda k: f32(2.0 ** k)
+    (W1, b1), (W2, b2), (W3, _) = [(w.numpy().astype(f32), b.numpy().astype(f32)) for w, b in layers]
+    xyz, nx, idx = xyz.numpy().astype(f32), nx.numpy().astype(f32), gidx.numpy().astype(np.int64)
+    out, arg, g = out.numpy().astype(f32), arg.numpy().astype(np.int64), g.numpy().astype(f32)
+    M, N = nx.shape[0], xyz.shape[0]
+    k1 = sa_k(max(np.abs(W1).max(), np.abs(b1).max()))
+    k2, k3 = sa_k(np.abs(W2).max()), sa_k(np.abs(W3).max())
+    EW1, EB1 = l1_exponent(np.abs(W1).sum(1, dtype=f32).max()), l1_exponent(np.abs(b1).max())
+    EW2, EB2 = l1_exponent(np.abs(W2).sum(1, dtype=f32).max()), l1_exponent(np.abs(b2).max())
+    EW3T = l1_exponent(np.abs(W3).sum(0, dtype=f32).max())
+    w1h, w1l = split16(W1 * p2(k1))
+    b1h, b1l = split16(b1 * p2(k1))
+    w2h, w2l = split16(W2 * p2(k2))
+    w3h, w3l = split16(W3 * p2(k3))
+    kd = -k3 - EW3T
+    loud = kg_lo is None
+    if loud:
+        kg_lo = max(14 + k2 - EW3T, 13)
+    dp = np.zeros((M, 64, 3), dtype=f32)
+    flips = {}
+    for (layer, m, s, c) in flip:
+        flips.setdefault((layer, m), []).append((s, c))
+    for m in range(M):
+        d = xyz[idx[m]] - nx[m]
+        kp = sa_k(np.abs(d).max(), 126, 154)
+        ph, pl = split16(d * p2(kp))
+        one = p2(kp)
+        z1 = (F(ph) @ F(w1h).T + F(b1h) * one + F(pl) @ F(w1h).T + F(b1l) * one + F(ph) @ F(w1l).T + F(pl) @ F(w1l).T).astype(f32)
+        e1 = max(EW1 + 14 - kp, EB1) + 1
+        kx = 14 - e1 - k1 - kp
+        ka = k1 + kp + kx + k2
+        xh, xl = split16(np.maximum(z1, f32(0)) * p2(kx))
+        a2 = (b2 * p2(ka) + _mm3(xh, xl, w2h, w2l)).astype(f32)
+        gate1, gate2 = z1 > 0, a2 > 0
+        for s, c in flips.get((1, m), []):
+            gate1[s, c] = ~gate1[s, c]
+        for s, c in flips.get((2, m), []):
+            gate2[s, c] = ~gate2[s, c]
+        g0 = np.where(out[m] > 0, g[m], f32(0)).astype(f32)
+        kg = sa_k(np.abs(g0).max(), kg_lo)
+        gh, gl = split16(g0 * p2(kg))
+        hot = arg[m][None, :] == np.arange(64)[:, None]                       # [64 s][128 ch]
+        if defect == "mask_block0":
+            hot[32:] = hot[:32]
+        if defect == "skip_ks3":
+            hot[:, 112:] = False
+        Bh, Bl = np.where(hot, gh[None, :], np.float16(0)), np.where(hot, gl[None, :], np.float16(0))
+        d2 = np.where(gate2, _mm3(Bh, Bl, w3h.T, w3l.T), f32(0)).astype(f32)
+        eh, el = split16(d2 * p2(kd))
+        if defect == "skip_ks2":
+            eh[:, 48:], el[:, 48:] = 0, 0                                      # positions 48-63 hold channels 48-63 (sa_perm)
+        d1 = _mm3(eh, el, w2h.T, w2l.T)
+        v = np.where(gate1, d1, f32(0)).astype(f32)
+        r = (v @ W1).astype(f32) * p2(-(k2 + kd + k3 + kg))
+        if defect == "no_hcb":
+            r[:32] = r[32:]
+        if loud and np.abs(g0).max() > 0 and biased_exponent(np.abs(g0).max()) < kg_lo:
+            r[:] = np.nan
+        dp[m] = r
+    pad = idx == idx[:, :1]
+    pad[:, 0] = False
+    dnew = -dp.sum(1, dtype=f32)
+    merged = np.where(pad[..., None], f32(0), dp)
+    if defect != "no_ex":
+        merged[:, 0] += np.where(pad[..., None], dp, f32(0)).sum(1, dtype=f32)
+    return torch.from_numpy(merged), torch.from_numpy(dnew), torch.from_numpy(sa1_scatter_fixed(merged, idx, N))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -8,8 +8,9 @@ Bounded (the bounds of tests/test_gpu_pn2_kernels.py; plain fp32 sums without th
 forward, three chained split layers: R.sa1_fwd), shift, rt, out2 / arg2 / m0 / m1, h1, h2, p3 / arg3, q1, q2, logits; after the
 backward g256, g512, g1024, dh2, dh1, dout2, dr, g1, the final dnx2 (level 3's coordinate gradient minus the centres' share),
 the final dnx1 (W_x^T dr + dnx2 scattered by idx2 + gnx1) and dx (gxyz + dnx1 scattered by idx1, planar).
-Taken as given: level 1's BACKWARD (gxyz, gnx1): it recomputes its gates in the kernel, so a lone bound needs a margin
-scheme of its own; test_fused_first_level_operator covers it."""
+Level 1's BACKWARD recomputes its gates in the kernel: gnx1 and the level's own gxyz are held to R.sa1_bwd + its allowance for
+the gates inside their bands (tests/test_gpu_pn2_sa1_bwd.py), computed from the GPU's own out1, arg1 and g1; where the
+single-stream form accumulates the scatter of dnx1 into gxyz in place, the sum is held."""
 import ctypes
 
 import pytest
@@ -202,10 +203,25 @@ def test_native_ssg_stage_by_stage(B, N, side, monkeypatch):
     dnx1 = f32(K["dnx1"], B, 512, 3)
     bound(dnx1, sc + gnx1.double(), R.tolerance(sc + gnx1.double(), smag - base.abs() + bmag + gnx1.double().abs(), 128 + most + 1),
           "dnx1 " + tag)
-    # dx = planar(gxyz + dnx1 scattered by idx1)
+    # ---- level 1's backward, from the GPU's own out1 / arg1 / g1: gnx1 = dnew, gxyz = dxyz (+ the scatter of dnx1 by idx1 where
+    # that went into gxyz in place), under bound + allowance
     gxyz = f32(K["gxyz"], B, N, 3)
+    sc, smag, most = R.scatter_rows3(dnx1.double(), idx1, N)
+    worst = {"gnx1": 0.0, "gxyz": 0.0}
+    for b in range(B):
+        rb1 = R.sa1_bwd(xyz[b], nx1[b], gidx1[b], L1, out1_[b], arg1[b], g1.reshape(B, 512, 128)[b])
+        ref, _, tol, allow = rb1["dnew"]
+        worst["gnx1"] = max(worst["gnx1"], R.worst_ratio(gnx1[b], ref, tol + allow))
+        ref, mag, tol, allow = rb1["dxyz"]
+        if side != "1":
+            tol = tol + R.tolerance(ref + sc[b], mag + smag[b], most + 1)
+            ref = ref + sc[b]
+        worst["gxyz"] = max(worst["gxyz"], R.worst_ratio(gxyz[b], ref, tol + allow))
+    for name, ratio in worst.items():
+        print("worst err/tol %-40s %.4f" % (name + " " + tag, ratio))
+        assert ratio <= 1.0, "%s: worst err / tol = %g" % (name, ratio)
+    # dx = planar(gxyz + dnx1 scattered by idx1)
     if side == "1":      # the scatter went into a buffer of its own (the forward's f1), added on the way out
-        sc, smag, most = R.scatter_rows3(dnx1.double(), idx1, N)
         gx2 = f32(K["f1"], B, N, 3)
         bound(gx2, sc, R.tolerance(sc, smag, most), "gx2 " + tag)
         ref, mag = gxyz.double() + gx2.double(), gxyz.double().abs() + gx2.double().abs()

@@ -306,6 +306,10 @@ def test_debug_entries_refuse_null_pointers_and_sizes_outside_the_contract():
     assert lib.geoa3_debug_pn2_sa2b(*ok14, 0, None) == EINVAL
     assert lib.geoa3_debug_pn2_sa2b(*(ok14[:10] + [p + 8] + ok14[11:]), 1, None) == EINVAL       # scratch not 256-byte aligned
     assert lib.geoa3_debug_pn2_sa2b(*(ok14[:13] + [None]), 1, None) == EINVAL
+    assert lib.geoa3_debug_pn2_sa1_scatter(None, p, 1, 40, 8, p, None) == EINVAL
+    assert lib.geoa3_debug_pn2_sa1_scatter(p, p, 0, 40, 8, p, None) == EINVAL
+    assert lib.geoa3_debug_pn2_sa1_scatter(p, p, 1, 40, 8, None, None) == EINVAL
+    assert lib.geoa3_debug_pn2_sa1_scatter(p, p, 1, 7000, 8, p, None) == -3      # one instance's sums beyond LDS: not supported
     assert lib.geoa3_debug_pn2_sa2b_scratch_bytes(0) == 0
     per = lib.geoa3_debug_pn2_sa2b_scratch_bytes(1)
     assert per == R.sa2b_scratch_layout()[1] and lib.geoa3_debug_pn2_sa2b_scratch_bytes(5) == 5 * per
@@ -323,7 +327,7 @@ def test_chained_restatements_are_the_oracle_forward_and_input_gradient(N):
     """float64 throughout (the sampler and the ball queries pick in float32, as the oracle's do): sa1_fwd -> sa2_pre -> affine3 -> sa2_fwd ->
     conv -> conv -> conv_pool -> fc x 3 gives oracle.pointnet2_ssg_forward; fc x 3 -> wide_bwd -> conv x 2 -> affine3_grad ->
     sa2_bwd -> sa2_pre (W_f^T) -> scatter_rows3, with level 1's forward restatement (sa1_fwd) differentiated by autograd (its
-    backward is not restated: DESIGN 8b), gives its input gradient."""
+    backward's restatement, sa1_bwd, is pinned to autograd on its own below), gives its input gradient."""
     from oracle import geoa3_oracle as O
     from oracle import pointnet2_oracle as P2
     B = 2
@@ -407,3 +411,163 @@ def test_sa1_fwd_bound_notices_a_lost_term_and_reads_float32_differences():
     ratio = R.worst_ratio(f32["out"], r["out"], r["tol_out"])
     print("cpu fp32 err/tol sa1_fwd: %.4f" % ratio)
     assert ratio <= 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# level 1's backward: sa1_bwd_kernel + sa1_scatter_kernel
+# ---------------------------------------------------------------------------------------------------------------------
+SA1B_PLAIN = [s + ("random",) for s in C.SA1B_SHAPES] + [(1, 8, 80, v) for v in ("padding", "padding_arg", "zeros")] + \
+             [C.SA1B_BAND]
+SA1B_ALL = SA1B_PLAIN + [(1, 8, 80, v) for v in C.SA1B_STRESS]
+
+
+@pytest.mark.parametrize("B,M,N,variant", SA1B_PLAIN)
+def test_sa1_bwd_restatement_is_autograd_of_gather_mlp_max(B, M, N, variant):
+    """float64 autograd through gather -> minus the centroid -> three layers -> the sample arg names -> relu, at float64 copies
+    of the case's inputs: d xyz == dxyz, d new_xyz == dnew, the gradient of the differences with the padded samples merged
+    into sample 0 == dp"""
+    c = C.sa1b_case(B, M, N, variant)
+    L = [(w.double(), b.double()) for w, b in c["layers"]]
+    for b in range(min(B, 3)):
+        x, nx = c["xyz"][b].double().requires_grad_(True), c["nx"][b].double().requires_grad_(True)
+        d = x[c["gidx"][b].long().reshape(-1)].reshape(M, 64, 3) - nx.unsqueeze(1)
+        d.retain_grad()
+        y3 = F.relu(F.relu(d @ L[0][0].t() + L[0][1]) @ L[1][0].t() + L[1][1]) @ L[2][0].t() + L[2][1]
+        at = torch.gather(y3, 1, c["arg"][b].long().unsqueeze(1)).squeeze(1)
+        live = (c["out"][b] > 0).double()
+        (at * live * c["g"][b].double()).sum().backward()
+        r = R.sa1_bwd(x.detach(), nx.detach(), c["gidx"][b], L, c["out"][b], c["arg"][b], c["g"][b])
+        scale = float(d.grad.abs().max()) + 1e-300
+        assert torch.allclose(r["dxyz"][0], x.grad, rtol=1e-10, atol=1e-12 * scale)
+        assert torch.allclose(r["dnew"][0], nx.grad, rtol=1e-10, atol=1e-12 * scale)
+        assert torch.allclose(r["dp"][0], R.merge_padding(d.grad, r["pad"]), rtol=1e-10, atol=1e-12 * scale)
+        assert bool((r["dp"][1] >= r["dp"][0].abs() * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize("B,M,N,variant", SA1B_ALL)
+def test_sa1_bwd_share_cap_lost_terms_and_emulation(B, M, N, variant):
+    """From the reference alone: at most 1e-3 of the case's non-padded dp rows carry an allowance.  In every case that is not
+    a stress case one lost term -- a channel of W3^T dz3, a k of the W2^T product, a row of the K = 3 contraction, a sample of
+    dnew's sum, a merged duplicate (where arg names one), an (m, s) entry of a destination -- moves an entry past bound +
+    allowance.  The emulation of the kernels' arithmetic stays inside it (stress cases included), and so does a plain float32
+    evaluation of the restatement."""
+    c, refs = C.sa1b_case(B, M, N, variant), C.sa1b_reference(B, M, N, variant)
+    share = C.sa1b_share(refs)
+    print("share of rows with an allowance %s %s: %.2e" % ((B, M, N), variant, share))
+    assert share <= C.SA1B_SHARE
+    L = [(w.double(), b.double()) for w, b in c["layers"]]
+    r0 = refs[0]
+    if variant not in C.SA1B_STRESS:
+        mag_rows = r0["dp"][1].sum(-1) * (~r0["pad"])
+        m, s = divmod(int(mag_rows.argmax()), 64)                                  # the non-padded row with the most behind it
+        g0 = torch.where(c["out"][0, m] > 0, c["g"][0, m], torch.zeros(128)) * (c["arg"][0, m].long() == s)
+        fw = C._sa1_fwd64(c, 0)                                                    # (a k / a row whose gate is open at that row)
+        lost = [("ch", (m, s, int(g0.abs().argmax()))), ("k2", int(fw["z2"][m, s].argmax())), ("row", int(fw["z1"][m, s].argmax())),
+                ("sample", (m, s)), ("entry", (m, s))]
+        if variant == "padding_arg":
+            lost.append(("dup", (0, 63)))
+        for lose in lost:
+            bad = R.sa1_bwd(c["xyz"][0], c["nx"][0], c["gidx"][0], L, c["out"][0], c["arg"][0], c["g"][0], lose=lose)
+            moved = max(R.worst_ratio(bad[k][0], r0[k][0], r0[k][2] + r0[k][3]) for k in ("dp", "dnew", "dxyz"))
+            assert moved > 1.0, (lose, moved)
+    few = min(B, 3)          # (clouds are independent on the CPU: three of the five are enough here)
+    C.sa1b_checks(refs[:few], *C.sa1b_emulate(dict(c, B=few)), "cpu emulation sa1_bwd %s %s" % ((B, M, N), variant))
+    f32 = [R.sa1_bwd(c["xyz"][0], c["nx"][0], c["gidx"][0], c["layers"], c["out"][0], c["arg"][0], c["g"][0])]
+    C.sa1b_checks(refs[:1], *[[r[k][0] for r in f32] for k in ("dp", "dnew", "dxyz")], "cpu fp32 sa1_bwd %s %s" % ((B, M, N), variant))
+
+
+def test_sa1_bwd_allowance_is_what_admits_an_in_band_gate():
+    """The `band` case: one z1 and one z2 of a row that carries gradient sit inside their bands.  The emulation with either of
+    those gates as it computes them AND inverted stays inside bound + allowance; of each pair one side misses the plain bound:
+    the margin scheme is necessary, not merely loose."""
+    sh = C.SA1B_BAND
+    c, refs = C.sa1b_case(*sh), C.sa1b_reference(*sh)
+    assert len(c["band"]) == 2
+    L = [(w.double(), b.double()) for w, b in c["layers"]]
+    f = C._sa1_fwd64(c, 0)
+    for (layer, b, m, s, ch) in c["band"]:
+        z, t = (f["z1"], f["t1"]) if layer == 1 else (f["z2"], f["t2"])
+        assert float(z[m, s, ch].abs()) <= float(t[m, s, ch]) and float(refs[0]["dp"][3][m, s if not refs[0]["pad"][m, s] else 0].max()) > 0
+        plain = []
+        for flip in ((), ((layer, b, m, s, ch),)):
+            got = C.sa1b_emulate(c, flip=flip)
+            C.sa1b_checks(refs, *got, "band gate %d flipped %d" % (layer, len(flip)))
+            plain.append(max(R.worst_ratio(got[i][0], refs[0][k][0], refs[0][k][2]) for i, k in enumerate(("dp", "dnew", "dxyz"))))
+        print("plain err/tol with the layer-%d gate as computed / inverted: %.3g %.3g" % (layer, plain[0], plain[1]))
+        assert max(plain) > 1.0
+
+
+@pytest.mark.parametrize("defect,variant", [("no_ex", "padding_arg"), ("mask_block0", "padding"), ("skip_ks3", "padding"),
+                                            ("skip_ks2", "padding"), ("no_hcb", "padding")])
+def test_sa1_bwd_bounds_notice_the_kernel_defects(defect, variant):
+    """the emulation with one of the kernel's steps broken -- the merged duplicates dropped from sample 0, the one-hot mask of
+    the wrong column block, the last k-step of either backward product skipped, the column block's selection removed -- misses
+    the bounds of the padding cases"""
+    sh = (1, 8, 80, variant)
+    c, refs = C.sa1b_case(*sh), C.sa1b_reference(*sh)
+    with pytest.raises(AssertionError):
+        C.sa1b_checks(refs, *C.sa1b_emulate(c, defect=defect), "defect " + defect)
+
+
+def test_sa1_scatter_model_bound_and_order_independence():
+    """the integer model of sa1_scatter_kernel: within cnt 2^(Ex - 41) + 2^-24 |sum| of the float64 sum; the same bits with
+    the centroids and the samples behind sample 0 in any order; a NaN row poisons its destination, an infinite one the
+    instance; padded samples are skipped whatever they hold"""
+    c = C.sa1b_case(3, 40, 300)
+    dp = C.sa1b_emulate(c)[0][1].numpy()
+    gidx = c["gidx"][1].numpy()
+    got = R.sa1_scatter_fixed(dp, gidx, 300)
+    ref, bound, Ex = R.sa1_scatter_bound(dp, gidx, 300)
+    assert 2.0 ** (Ex - 1) <= float(np.abs(dp).max()) < 2.0 ** Ex
+    ratio = R.worst_ratio(torch.from_numpy(got), ref, bound)
+    print("scatter model err/bound %.4f" % ratio)
+    assert ratio <= 1.0
+    rng = np.random.default_rng(5)
+    pm = rng.permutation(40)
+    dp2, g2 = dp[pm].copy(), gidx[pm].copy()
+    for m in range(40):
+        ps = np.concatenate([[0], 1 + rng.permutation(63)])
+        dp2[m], g2[m] = dp2[m][ps], g2[m][ps]
+    assert np.array_equal(R.sa1_scatter_fixed(dp2, g2, 300).view(np.uint32), got.view(np.uint32))
+    pad = R.pad_mask(torch.from_numpy(gidx)).numpy()
+    junk = dp.copy()
+    junk[pad] = 7.0                                   # (below the instance's maximum?  no: it moves Ex, as in the kernel)
+    assert R.sa1_scatter_fixed(junk, gidx, 300).shape == got.shape
+    small = dp.copy()
+    small[pad] = np.float32(2.0 ** (Ex - 30))
+    assert np.array_equal(R.sa1_scatter_fixed(small, gidx, 300).view(np.uint32), got.view(np.uint32))
+    nan = dp.copy()
+    nan[5, 0, 1] = np.nan
+    out = R.sa1_scatter_fixed(nan, gidx, 300)
+    assert np.isnan(out[gidx[5, 0]]).all() and np.isfinite(np.delete(out, gidx[5, 0], 0)).all()
+    inf = dp.copy()
+    inf[5, 0, 1] = np.inf
+    assert np.isnan(R.sa1_scatter_fixed(inf, gidx, 300)).all()
+    assert not R.sa1_scatter_fixed(np.zeros_like(dp), gidx, 300).any()
+
+
+def test_sa1_bwd_emulation_follows_small_gradients():
+    """grad_out times 2^-s in the emulation: with the scale's exponent field clamped at 110 (the kernel as it was) the scale-free
+    bound is missed from a centroid maximum of about 2^-34 on, and from 2^-50 on every result is an exact zero; with the clamp
+    the format allows (Emin = max(13, 14 + k2 - EW3T)) the bound holds down to a maximum of 2^(Emin - 127), and below it the
+    centroid's results are NaN"""
+    sh = (1, 8, 80)
+    c, refs = C.sa1b_case(*sh), C.sa1b_reference(*sh)
+    r = refs[0]
+    (_, _), (W2, _), (W3, _) = c["layers"]
+    Emin = max(13, 14 + R.sa_k(float(W2.abs().max())) - R.l1_exponent(float(W3.abs().sum(0).max())))
+    g0 = torch.where(c["out"][0] > 0, c["g"][0], torch.zeros(()))
+    Es = [R.biased_exponent(float(v)) for v in g0.abs().max(1).values]
+    ratio = lambda got, s: max(R.worst_ratio(got[i][0], r[k][0] * 2.0 ** -s, (r[k][2] + r[k][3]) * 2.0 ** -s)
+                               for i, k in enumerate(("dp", "dnew")))
+    was = {s: ratio(C.sa1b_emulate(dict(c, g=c["g"] * 2.0 ** -s), kg_lo=110), s) for s in (16, 32, 40, 56)}
+    print("cpu emulation, clamp at 110: " + " ".join("2^-%d %.3g" % kv for kv in was.items()))
+    assert was[16] <= 1.0 and was[32] <= 1.0 and was[40] > 1.0 and was[56] > 1.0
+    assert not C.sa1b_emulate(dict(c, g=c["g"] * 2.0 ** -56), kg_lo=110)[0].any()
+    worst = 0.0
+    for s in range(20, min(Es) - Emin + 1, 4):
+        worst = max(worst, ratio(C.sa1b_emulate(dict(c, g=c["g"] * 2.0 ** -s)), s))
+    print("cpu emulation, derived clamp: worst err/tol down to 2^-%d: %.4f" % (min(Es) - Emin, worst))
+    assert worst <= 1.0
+    dp, dnew, _ = C.sa1b_emulate(dict(c, g=c["g"] * 2.0 ** -(max(Es) - Emin + 4)))
+    assert bool(torch.isnan(dnew).all()) and bool(torch.isnan(dp[0][~r["pad"]]).all())
