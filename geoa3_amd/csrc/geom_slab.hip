@@ -226,6 +226,44 @@ __device__ __forceinline__ float slab_compact(uint16_t* cand, float* candd, int 
   return kth;
 }
 
+// One staging chunk of the sorted cloud -- coordinates and original indices of cn <= SK_CHUNK points from c0 on -- on its way
+// to LDS.  request() issues every load of the thread without a wait between them (a loop of load / wait / LDS write is one
+// round trip to memory per trip: four of them per chunk, all workgroups of a launch in the same phase); commit() writes them.
+// What the caller puts between the two runs under the loads' latency.  Sixteen dwords per thread (16-byte loads for the
+// instances whose rows are aligned were tried: the compiler merges the two forms' registers and waits for everything in
+// flight before the second); the addresses are clamped, not predicated (a branch around a load brings its wait along).
+// Elements [cn, cn4) are padded with NaN coordinates: the distance is NaN and `d <= tau` is false.
+struct SlabRun {
+  static constexpr int T = SK_CHUNK / SK_BLOCK;
+  float x[T], y[T], z[T];
+  int32_t id[T];
+  __device__ __forceinline__ void request(const float* __restrict__ Sb, const int32_t* __restrict__ Ib, int N, int c0, int cn,
+                                          int tid) {
+#pragma unroll
+    for (int u = 0; u < T; ++u) {
+      const int j = c0 + max(min(tid + u * SK_BLOCK, cn - 1), 0);
+      x[u] = Sb[j];
+      y[u] = Sb[N + j];
+      z[u] = Sb[2 * N + j];
+      id[u] = Ib[j];
+    }
+  }
+  __device__ __forceinline__ void commit(float* s_ref, uint16_t* s_id, int cn, int tid) const {
+    const int cn4 = (cn + 3) & ~3;
+#pragma unroll
+    for (int u = 0; u < T; ++u) {
+      const int j = tid + u * SK_BLOCK;
+      if (j < cn4) {
+        const bool ok = j < cn;
+        s_ref[j] = ok ? x[u] : __builtin_nanf("");
+        s_ref[SK_CHUNK + j] = ok ? y[u] : __builtin_nanf("");
+        s_ref[2 * SK_CHUNK + j] = ok ? z[u] : __builtin_nanf("");
+        s_id[j] = ok ? (uint16_t)id[u] : (uint16_t)0;
+      }
+    }
+  }
+};
+
 template <int CAP>
 __global__ __launch_bounds__(SK_BLOCK) void knn_slab_kernel(const float* __restrict__ R, int N, int K,
                                                             const int32_t* __restrict__ prior,
@@ -312,15 +350,10 @@ __global__ __launch_bounds__(SK_BLOCK) void knn_slab_kernel(const float* __restr
     for (int c0 = c_lo; c0 < c_hi; c0 += SK_CHUNK) {
       const int cn = min(SK_CHUNK, c_hi - c0);
       const int cn4 = (cn + 3) & ~3;
+      SlabRun run;
+      run.request(Sb, Ib, N, c0, cn, tid);   // (in flight across the barrier: the last chunk's readers are what it waits for)
       __syncthreads();
-      for (int j = tid; j < cn4; j += SK_BLOCK) {
-        const bool ok = j < cn;
-        // pad with NaN coordinates: the distance is NaN and `d <= tau` is false
-        s_ref[j] = ok ? Sb[c0 + j] : __builtin_nanf("");
-        s_ref[SK_CHUNK + j] = ok ? Sb[N + c0 + j] : __builtin_nanf("");
-        s_ref[2 * SK_CHUNK + j] = ok ? Sb[2 * N + c0 + j] : __builtin_nanf("");
-        s_id[j] = ok ? (uint16_t)Ib[c0 + j] : (uint16_t)0;
-      }
+      run.commit(s_ref, s_id, cn, tid);
       __syncthreads();
       // the next four candidates are requested before this step's appends (LDS stores the loads may not be moved across):
       // two waves per SIMD do not hide an LDS round trip per step (the last step's extra read stays inside the arrays)
@@ -402,6 +435,24 @@ __device__ __forceinline__ void sp_count_less(int& r, unsigned long long kj, uns
   asm volatile("v_cmp_lt_u64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc" : "+v"(r) : "v"(kj), "v"(ki) : "vcc");
 }
 
+#ifdef GEOA3_SP_STAMPS   // probe build: s_memtime at the phase boundaries of eight workgroups of <32, false> (tools/sp_stamps.py)
+__device__ unsigned long long g_sp_stamps[8 * 16];
+#define SP_STAMP(i)                                                                                                    \
+  do {                                                                                                                 \
+    if (!MULTI && tid == 0 && blockIdx.x == 1 && (blockIdx.y & 31) == 7 && blockIdx.y < 256)                           \
+      g_sp_stamps[(blockIdx.y >> 5) * 16 + (i)] = __builtin_amdgcn_s_memtime();                                        \
+  } while (0)
+// ... once v has arrived (a stamp behind loads that nothing has used yet would be taken while they are in flight)
+#define SP_STAMP_AFTER(i, v)                                                                                           \
+  do {                                                                                                                 \
+    asm volatile("" ::"v"(v));                                                                                         \
+    SP_STAMP(i);                                                                                                       \
+  } while (0)
+#else
+#define SP_STAMP(i)
+#define SP_STAMP_AFTER(i, v)
+#endif
+
 // Lists of 32 slots at four waves per SIMD (round 4).  With 40 slots the final ranking's keys (80 registers) spilled 35
 // registers at the 128 of four waves -- 140 bytes of scratch per lane, 36 MB each way per launch at 250 instances; at three
 // waves (168 VGPRs) nothing spilled but the kernel alone took 116 instead of 101 us.  32 slots: 8 bytes of scratch, the list
@@ -437,11 +488,18 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
   const int32_t* bs = bstart + (size_t)b * SB_PITCH;
   const SlabGeo g = geo[b];
   const int pc = live ? pos : N - 1;
+  // Every load of the prologue is requested before the first wait (the launch is one round of workgroups, all in the same
+  // phase: nothing else is resident to cover a round trip to memory, and the loops this replaces made 33 of them one after
+  // the other).  First the query's original index -- the rows of the old table hang on it --, then its coordinates.
+  const int qo = Ib[pc];
   const float qx = Sb[pc], qy = Sb[N + pc], qz = Sb[2 * N + pc];
-  float nqx, nqy, nqz;
-  slab_negq(qx, qy, qz, nqx, nqy, nqz);
-  const int qo = Ib[pc];                                     // the query's original index
-  if (tid == 0) {
+  SP_STAMP(0);
+  // !MULTI: the sorted cloud is one chunk, so what the scan reads does not depend on the windows: it is requested here and
+  // lands in LDS behind the seed radius's walk (profiles/knn_slabp_phases.txt)
+  constexpr bool EARLY = !MULTI;
+  SlabRun run;
+  if (EARLY && prior == nullptr) run.request(Sb, Ib, N, 0, N, tid);
+  if (!EARLY && tid == 0) {
     s_lo = SB_NB;
     s_hi = -1;
   }
@@ -452,16 +510,39 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
     // 64 K consecutive elements of ~4 rows per load instruction instead of 64 rows), then every thread walks its row.
     float* const s_org = reinterpret_cast<float*>(s_un);
     uint16_t* const s_pri = reinterpret_cast<uint16_t*>(s_un + 3 * SK_CHUNK * 4);
-    for (int j = tid; j < 3 * N; j += SK_BLOCK) s_org[j] = Rb[j];
-    s_id[tid] = (uint16_t)qo;
-    __syncthreads();
+    // the cloud: 3 N <= 3 SK_CHUNK floats, twelve dwords per thread
+    constexpr int CT = 3 * SK_CHUNK / SK_BLOCK;
+    const int n3 = 3 * N;
+    float cl[CT];
+#pragma unroll
+    for (int u = 0; u < CT; ++u) cl[u] = Rb[min(tid + u * SK_BLOCK, n3 - 1)];
+    // the old rows: a wavefront's 64 K <= 64 SP_KMAX elements, every gather requested before the first range check (the
+    // rows' original indices come from the wavefront's own lanes)
     const int w0 = tid & ~63, lane = tid & 63;
     const float inv_k = 1.0f / (float)K;
-    for (int e = lane; e < 64 * K; e += 64) {
+    int32_t pv[SP_KMAX];
+    SP_STAMP_AFTER(1, qo);
+#pragma unroll
+    for (int u = 0; u < SP_KMAX; ++u) {
+      const int e = min(lane + 64 * u, 64 * K - 1);
       const int row = (int)(((float)e + 0.5f) * inv_k), m = e - row * K;
-      const int32_t v = prior[((size_t)b * N + s_id[w0 + row]) * K + m];
-      s_pri[w0 * K + e] = (uint16_t)(v < 0 || v >= N ? 0xffff : v);
+      pv[u] = prior[((size_t)b * N + __shfl(qo, row, 64)) * K + m];
     }
+    if constexpr (EARLY) run.request(Sb, Ib, N, 0, N, tid);   // (last: the seed radius does not wait for it)
+    // (no predicate: s_org holds 3 SK_CHUNK floats whatever N is, and nothing reads beyond 3 N -- a store under `j < 3 N`
+    // takes its load along into the branch, with a wait of its own)
+#pragma unroll
+    for (int u = 0; u < CT; ++u) s_org[tid + u * SK_BLOCK] = cl[u];
+    SP_STAMP(2);
+    // (opaque: a gather whose only use is the predicated store below is moved into its branch, behind a wait of its own)
+#pragma unroll
+    for (int u = 0; u < SP_KMAX; ++u) asm volatile("" : "+v"(pv[u]));
+#pragma unroll
+    for (int u = 0; u < SP_KMAX; ++u) {
+      const int e = lane + 64 * u;
+      if (e < 64 * K) s_pri[w0 * K + e] = (uint16_t)(pv[u] < 0 || pv[u] >= N ? 0xffff : pv[u]);
+    }
+    SP_STAMP(3);
     __syncthreads();
     if (live) {
       float t = 0.f;
@@ -499,7 +580,10 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
     if (ok) tau = t;
   }
   if (!live) tau = -1.f;  // padding lanes never collect candidates
-  __syncthreads();
+  SP_STAMP(4);
+  float nqx, nqy, nqz;
+  slab_negq(qx, qy, qz, nqx, nqy, nqz);
+  if (!EARLY) __syncthreads();
   int blo = SB_NB, bhi = -1;
   if (live) {
     blo = 0;
@@ -510,15 +594,26 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
       blo = slab_bin(qa - r, g.lo, g.inv_w);
       bhi = slab_bin(qa + r, g.lo, g.inv_w);
     }
-    atomicMin(&s_lo, blo);
-    atomicMax(&s_hi, bhi);
+    if (!EARLY) {
+      atomicMin(&s_lo, blo);
+      atomicMax(&s_hi, bhi);
+    }
   }
-  // the workgroup stages the union of its 256 windows; a WAVEFRONT scans only the union of its own 64 (the queries are
-  // consecutive along the slab axis: ~2/3 of the workgroup's run)
+  // the workgroup stages the union of its 256 windows (EARLY: the whole sorted cloud); a WAVEFRONT scans only the union of
+  // its own 64 (the queries are consecutive along the slab axis: ~2/3 of the workgroup's run)
   const int w_blo = -(int)wave_max(-(float)blo), w_bhi = (int)wave_max((float)bhi);
   int wv_lo = w_blo <= w_bhi ? bs[w_blo] : 0, wv_hi = w_blo <= w_bhi ? bs[w_bhi + 1] : 0;
+  // (EARLY: the window's two bin starts are on their way while the run is written; the barrier also ends the seed phase's
+  // use of the lists' LDS)
+  if constexpr (EARLY) run.commit(s_ref, s_id, N, tid);
+  SP_STAMP(5);
   __syncthreads();
-  int c_lo = bs[s_lo], c_hi = bs[s_hi + 1];
+  int c_lo = 0, c_hi = N;
+  if constexpr (!EARLY) {
+    c_lo = bs[s_lo];
+    c_hi = bs[s_hi + 1];
+  }
+  SP_STAMP_AFTER(6, wv_lo + wv_hi + c_lo + c_hi);
 
   // a thread's list: positions s_pos[slot][tid]; fill state = the BYTE offset of the next slot, cnt * 2 SK_BLOCK + 2 tid
   static_assert(SK_BLOCK == 256, "poff >> 9 is the count");
@@ -560,17 +655,12 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
     // pass 1 only runs if a (bad) prior left some lane with fewer than K candidates: everything, without pruning
    for (int c0 = c_lo; c0 < c_hi; c0 += SK_CHUNK) {      // (!MULTI: N <= SK_CHUNK, the whole run at once)
     const int cn = min(SK_CHUNK, c_hi - c0);
-    const int cn4 = (cn + 3) & ~3;
-    __syncthreads();
-    for (int j = tid; j < cn4; j += SK_BLOCK) {
-      const bool ok = j < cn;
-      // pad with NaN coordinates: the distance is NaN and `d <= tau` is false
-      s_ref[j] = ok ? Sb[c0 + j] : __builtin_nanf("");
-      s_ref[SK_CHUNK + j] = ok ? Sb[N + c0 + j] : __builtin_nanf("");
-      s_ref[2 * SK_CHUNK + j] = ok ? Sb[2 * N + c0 + j] : __builtin_nanf("");
-      s_id[j] = ok ? (uint16_t)Ib[c0 + j] : (uint16_t)0;
+    if constexpr (!EARLY) {   // (EARLY: staged in the prologue, and the full scan of pass 1 reads the same chunk)
+      run.request(Sb, Ib, N, c0, cn, tid);
+      __syncthreads();
+      run.commit(s_ref, s_id, cn, tid);
+      __syncthreads();
     }
-    __syncthreads();
     const int j_lo = min(max(wv_lo - c0, 0), SK_CHUNK - 4) & ~3, j_hi = (min(wv_hi - c0, cn) + 3) & ~3;
     float4 nx = *reinterpret_cast<const float4*>(&s_ref[j_lo]);
     float4 ny = *reinterpret_cast<const float4*>(&s_ref[SK_CHUNK + j_lo]);
@@ -616,6 +706,7 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
     wv_lo = 0;
     wv_hi = N;
   }
+  SP_STAMP(7);
 
   if constexpr (MULTI) {
     if (live) {
@@ -674,6 +765,7 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
     if (cls == 0) rank_out(C20);
     else if (cls == 1) rank_out(C28);
     else rank_out(CXX);
+    SP_STAMP(8);
     __syncthreads();
     const float inv_k = 1.0f / (float)K;
     const int rows = min(SK_BLOCK, N - (int)blockIdx.x * SK_BLOCK);
@@ -684,6 +776,7 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
       dists[o] = s_od[e];
       idx[o] = v == 0xffffu ? -1 : (int32_t)v;
     }
+    SP_STAMP(9);
   }
 }
 
@@ -743,6 +836,12 @@ extern "C" int64_t geoa3_knn_self_scratch_bytes(int B, int N) {
   const size_t a = knn_self_carve(nullptr, B, N, SB_PITCH, sizeof(SlabGeo)).total, g = geoa3_knn_cellgrid_scratch_bytes(B, N);
   return (int64_t)(a > g ? a : g);
 }
+
+#ifdef GEOA3_SP_STAMPS
+extern "C" int geoa3_debug_sp_stamps(unsigned long long* out) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sp_stamps), sizeof(g_sp_stamps)) == hipSuccess ? 0 : -1;
+}
+#endif
 
 extern "C" int geoa3_debug_knn_self_route(int B, int N, int K, int method, int has_prior, int scratch_ok) {
   if (!knn_self_sizes_ok(B, N, K)) return GEOA3_EINVAL;
