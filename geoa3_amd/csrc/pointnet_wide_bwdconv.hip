@@ -7,9 +7,10 @@
 //           channel) order inside a column.  PRE: one contiguous segment of the lists the FORWARD's finalize pass built
 //           per instance (wide_finalize_hits_kernel, pointnet_wide.hip), read in place; else built here, phases (1)-(2)
 //           of wide_max_bwd2_kernel (N > 4096, or the caller opted out: GEOA3_PN_NO_PRE_LISTS) -- same lists either way;
-//   walk    (3) the list cut into eight equal shares, one per wave; a column's sum in registers, list entries through
-//           SGPRs (scalar row / gradient addresses), eight weight rows in flight; shares that start inside a column go
-//           through side rows and are added in wave order;
+//   walk    (3) the list cut into eight equal shares, one per wave; a column's sum in registers; a wave holds 64 list
+//           entries at a time (one load; their gradients by one gather) and passes row, column and gradient through SGPRs;
+//           two batches of eight weight rows in flight; shares that start inside a column go through side rows and are
+//           added in wave order;
 //   product (4) tile gated by relu bits, scaled by a power of two from its own maximum and split ONCE into fp16 hi / lo
 //           images written over it; W2^T's fragments arrive split from the host (WideBwdArgs::W2th); four waves take one
 //           32 x 32 quadrant each on the f16 matrix core; the result leaves gated (or, first-layer form, is contracted
@@ -60,23 +61,28 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
   float* s_mx = s_side + BW2_WAVES * WM_CI;                             // [8] tile maxima of the waves
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y, m0 = blockIdx.x * COLS;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: the walk's list entries, rows and columns stay in SGPRs)
-  // requested now, used at the very end: the gate word of output row `lane`
-  unsigned long long gw2 = 0ull;
-  if (!GF && wave < 4) gw2 = a.Zmask2[((size_t)b * ((a.N + 63) >> 6) + blockIdx.x) * 64 + lane];
-  // ... and the gate words of tile rows 2 lane, 2 lane + 1 of the 128-channel activation
+  // requested now, used behind the walk: the gate words of tile rows 2 lane, 2 lane + 1 of the 128-channel activation
   const int tiles = (a.N + 63) >> 6;
   const ulonglong2 mkw = reinterpret_cast<const ulonglong2*>(a.Zmask + ((size_t)b * tiles + blockIdx.x) * WM_CI)[lane];   // rows 2 lane, 2 lane + 1
   const int qt = wave & 1, qc = (wave >> 1) & 1;     // waves 0-3: output rows 32 qt .., columns 32 qc ..
 
   // GF: [64] (w1 row, b1), then [2][32] partial d x -- in the side rows, once the walk is done with them
-  float4* s_w1 = reinterpret_cast<float4*>((reinterpret_cast<uintptr_t>(s_side) + 15) & ~(uintptr_t)15);
+  // (aligned as an index into smem, not as an integer address: the pointer stays an LDS pointer -- ds_read_b128, no flat loads)
+  float4* s_w1 = reinterpret_cast<float4*>(smem + (((int)(s_side - smem) + 3) & ~3));
   const float* gb = a.g + (size_t)b * a.Co;
   const int* argb = a.arg + (size_t)b * a.Co;
   const unsigned long long lt = (1ull << lane) - 1ull;
   BC_STAMP(0);
-  constexpr int U = 8;            // list entries (weight rows) in flight per wave in the walk
+  // the walk: a wave holds CH list entries at a time (lane u: entry c0 + u of its share) and keeps NB batches of U weight
+  // rows in flight -- the rows of batch k + NB - 1 are requested before batch k is accumulated
+  constexpr int U = 8, NB = 2, CH = 64;
   const int* seg = nullptr;       // PRE: the tile's segment of the instance's sorted hits
-  int ev0 = 0;                    // PRE: the wave's first U entries, requested before the tile is cleared
+  int ev0 = 0;                    // PRE: the wave's first CH entries, requested before the tile is cleared
+  // GF: row tid of the first layer's table, requested now and written to LDS once the walk is done with the side rows
+  float4 w1v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (GF) {
+    if (tid < 64) w1v = make_float4(a.w1[3 * tid], a.w1[3 * tid + 1], a.w1[3 * tid + 2], a.b1[tid]);
+  }
   if constexpr (PRE) {
     // the tile's lists are one contiguous segment of the instance's sorted hits (wide_finalize_hits_kernel)
     const int* ho = a.hoff + (size_t)b * (a.N + 1);
@@ -85,7 +91,7 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
     {
       const int tot = h1 - h0, per = (tot + BW2_WAVES - 1) / BW2_WAVES;
       const int lo = min(tot, wave * per), hi = min(tot, lo + per);
-      if (lo < hi) ev0 = seg[min(lo + (lane & (U - 1)), hi - 1)];
+      if (lo < hi) ev0 = seg[min(lo + lane, hi - 1)];
     }
     for (int e = tid; e < COLS * BC_PT; e += BW2_THREADS) s_acc[e] = 0.f;   // (while the offsets are on their way)
     if (tid <= COLS) s_off[tid] = hv - h0;
@@ -214,10 +220,11 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
     const int ldW = a.ldW ? a.ldW : WM_CI;   // (co * TAPS + tap) -th row of 128 input channels
     int cur = -1;
     float acc0 = 0.f, acc1 = 0.f;
-    // lane u holds entry h0 + u of the batch at h0 (PRE: as the forward wrote it, (co TAPS + tap) | column << 16, read from
-    // global one batch ahead; else the tile's own list in LDS, row | tile column << LSH); the entries travel through SGPRs
-    auto load_ev = [&](int h0) -> int {
-      const int i = min(h0 + (lane & (U - 1)), hi - 1);
+    // lane u holds entry c0 + u of the CH entries at c0 (PRE: as the forward wrote it, (co TAPS + tap) | column << 16, read
+    // from global one load ahead; else the tile's own list in LDS, row | tile column << LSH); an entry's row, column and
+    // gradient travel through SGPRs (v_readlane)
+    auto load_ev = [&](int c0) -> int {
+      const int i = min(c0 + lane, hi - 1);
       if constexpr (PRE) return seg[i];
       else return (int)s_list[i];
     };
@@ -244,51 +251,87 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
         *reinterpret_cast<float2*>(s_acc + cur * BC_PT + 2 * lane) = make_float2(acc0, acc1);
       }
     };
-    for (int h0 = lo; h0 < hi; h0 += U) {
-      float2 w[U];
-      float gg[U];
-      int cc[U];
-      // (v_readlane: the row address, the gradient's address and the column are scalar -- the walk was a quarter of the
-      //  kernel's VALU instructions)
-      const int ev = evn;
-      if (h0 + U < hi) evn = load_ev(h0 + U);
+    for (int c0 = lo; c0 < hi; c0 += CH) {
+      // the CH entries, decoded in place; their upstream gradients by ONE gather (lane u: the gradient of entry c0 + u --
+      // beyond the share the last entry again, never used) beside the first rows; the next CH entries behind them
+      const int ed = dec(evn);
+      const float gv = gb[(ed & ((1 << LSH) - 1)) / TAPS];
+      if (c0 + CH < hi) evn = load_ev(c0 + CH);
+      float2 w[NB][U];
+      // batch k of the CH entries: its weight rows (row addresses scalar, clamped as the entries are)
+      auto request = [&](int k, float2 (&wk)[U]) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool ok = h0 + u < hi;
-        const int e = dec(__builtin_amdgcn_readlane(ev, u));
-        const int er = e & ((1 << LSH) - 1);
-        w[u] = *reinterpret_cast<const float2*>(a.W + (size_t)er * ldW + 2 * lane);
-        gg[u] = ok ? gb[er / TAPS] : 0.f;
-        cc[u] = ok ? e >> LSH : -2;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (cc[u] == -2) break;
-        if (cc[u] != cur) {
-          flush();
-          cur = cc[u];
-          acc0 = 0.f;
-          acc1 = 0.f;
+        for (int u = 0; u < U; ++u) {
+          const int er = __builtin_amdgcn_readlane(ed, U * k + u) & ((1 << LSH) - 1);
+          wk[u] = *reinterpret_cast<const float2*>(a.W + (size_t)er * ldW + 2 * lane);
         }
-        acc0 += w[u].x * gg[u];
-        acc1 += w[u].y * gg[u];
+      };
+      // ... and its sums: the entries in list order, a column's terms in the order of its list
+      auto consume = [&](int k, const float2 (&wk)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (c0 + U * k + u >= hi) break;
+          const int c = __builtin_amdgcn_readlane(ed, U * k + u) >> LSH;
+          const float g = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gv), U * k + u));
+          if (c != cur) {
+            flush();
+            cur = c;
+            acc0 = 0.f;
+            acc1 = 0.f;
+          }
+          acc0 += wk[u].x * g;
+          acc1 += wk[u].y * g;
+        }
+      };
+#pragma unroll
+      for (int k = 0; k < CH / U + NB - 1; ++k) {
+        if (k < CH / U && c0 + U * k < hi) request(k, w[k % NB]);
+        if (k >= NB - 1) {
+          const int j = k - (NB - 1);
+          if (c0 + U * j >= hi) break;
+          consume(j, w[j % NB]);
+        }
       }
     }
     flush();
     if (lane == 0) s_sidecol[wave] = side_col;
     BC_STAMP(3);
   }
+  // the product's A operand: W2^T's fragments of waves 0-3, [qt][k-step][hi / lo][lane].  The first WQ k-steps are requested
+  // here, in front of the four barriers between the walk and the product, and each slot again as soon as its MFMAs are
+  // issued: the product waits for L2 once at the most
+  constexpr int WQ = 3;   // (the budget is 64 registers: scratch stays 0)
+  const half8* wf = reinterpret_cast<const half8*>(a.W2th) + (size_t)qt * 8 * 2 * 64 + lane;
+  half8 wq[WQ][2];
+  unsigned long long gw2 = 0ull;   // used at the very end: the gate word of output row `lane`
+  float x0 = 0.f, x1 = 0.f, x2 = 0.f;   // GF: the point of the thread's output column (the first layer's gate is recomputed from it)
+  if (wave < 4) {
+    if constexpr (!GF) gw2 = a.Zmask2[((size_t)b * tiles + blockIdx.x) * 64 + lane];
+#pragma unroll
+    for (int c = 0; c < WQ; ++c) {
+      wq[c][0] = wf[(2 * c) * 64];
+      wq[c][1] = wf[(2 * c + 1) * 64];
+    }
+    if constexpr (GF) {
+      const float* xp = a.x3 + (size_t)b * 3 * a.N + min(m0 + 32 * qc + (lane & 31), a.N - 1);
+      x0 = xp[0], x1 = xp[a.N], x2 = xp[2 * (size_t)a.N];
+    }
+  }
   __syncthreads();
   BC_STAMP(4);
   if (tid < WM_CI) {
+    int sc[BW2_WAVES];   // (read together: one LDS round trip in front of the additions instead of one per wave)
+#pragma unroll
+    for (int w = 1; w < BW2_WAVES; ++w) sc[w] = s_sidecol[w];
+#pragma unroll
     for (int w = 1; w < BW2_WAVES; ++w) {
-      const int c = s_sidecol[w];
+      const int c = sc[w];
       if (c >= 0) s_acc[c * BC_PT + tid] += s_side[w * WM_CI + tid];
     }
   }
   __syncthreads();
   BC_STAMP(5);
-  if (GF && tid < 64) s_w1[tid] = make_float4(a.w1[3 * tid], a.w1[3 * tid + 1], a.w1[3 * tid + 2], a.b1[tid]);    // (read behind the next barriers)
+  if (GF && tid < 64) s_w1[tid] = w1v;    // (read behind the next barriers)
   // (4) the 128 -> 64 layer behind it, on the tile while it is in LDS: gate by the relu bits of the 128-channel
   // activation, tile maximum -> power-of-two scale, and the tile is split ONCE, by all eight waves, into fp16 hi / lo
   // images written over it (row c: 128 hi halves, 128 lo halves, in the 528 bytes its 132 floats had); four waves then
@@ -330,32 +373,24 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
     *reinterpret_cast<half2v*>(row + WM_CI) = half2v{(_Float16)(x0 - (float)h0), (_Float16)(x1 - (float)h1)};
   }
   __syncthreads();
+  BC_STAMP(9);
   if (wave >= 4) return;
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const _Float16* brow = s_img + (32 * qc + (lane & 31)) * BC_PH + (lane >> 5) * 8;
-  {
-    const half8* wf = reinterpret_cast<const half8*>(a.W2th) + (size_t)qt * 8 * 2 * 64 + lane;   // [qt][c][hi / lo][lane]
-    constexpr int WQ = 2;   // k-steps of fragments in flight
-    half8 wq[WQ][2];
 #pragma unroll
-    for (int c = 0; c + 1 < WQ; ++c) {
-      wq[c][0] = wf[(2 * c) * 64];
-      wq[c][1] = wf[(2 * c + 1) * 64];
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (c + WQ - 1 < 8) {
-        wq[(c + WQ - 1) % WQ][0] = wf[(2 * (c + WQ - 1)) * 64];
-        wq[(c + WQ - 1) % WQ][1] = wf[(2 * (c + WQ - 1) + 1) * 64];
-      }
-      const half8 wh = wq[c % WQ][0], wl = wq[c % WQ][1];
-      const half8 xh = *reinterpret_cast<const half8*>(brow + c * 16);
-      const half8 xl = *reinterpret_cast<const half8*>(brow + WM_CI + c * 16);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc, 0, 0, 0);
+  for (int c = 0; c < 8; ++c) {
+    const half8 wh = wq[c % WQ][0], wl = wq[c % WQ][1];
+    const half8 xh = *reinterpret_cast<const half8*>(brow + c * 16);
+    const half8 xl = *reinterpret_cast<const half8*>(brow + WM_CI + c * 16);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc, 0, 0, 0);
+    if (c + WQ < 8) {
+      wq[c % WQ][0] = wf[(2 * (c + WQ)) * 64];
+      wq[c % WQ][1] = wf[(2 * (c + WQ) + 1) * 64];
+      __builtin_amdgcn_sched_barrier(0);   // (the scheduler would move the request down to its use: one L2 trip per k-step again)
     }
   }
   BC_STAMP(7);
@@ -368,8 +403,10 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
     const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int mq = m0 + 32 * qc + (ln & 31);
     const bool in = mq < a.N;
-    const float* xp = a.x3 + (size_t)b * 3 * a.N + (in ? mq : a.N - 1);
-    const float x0 = xp[0], x1 = xp[a.N], x2 = xp[2 * (size_t)a.N];
+    // what dx3 holds (the trunk's gradient), requested here for the sum at the very end; clamped like the point's address
+    float* dxp = a.dx3 + (size_t)b * 3 * a.N + (in ? mq : a.N - 1);
+    const float d0 = dxp[0], d1 = dxp[a.N], d2 = dxp[2 * (size_t)a.N];
+    __builtin_amdgcn_sched_barrier(0);   // (... and these behind the sums below)
     float q0 = 0.f, q1 = 0.f, q2 = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -388,10 +425,9 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
     __syncthreads();
     if (qt == 0 && ln < 32 && in) {
       const float4 o = s_q[qc * 32 + ln];
-      float* dxp = a.dx3 + (size_t)b * 3 * a.N + mq;    // += : the trunk's gradient is there already
-      dxp[0] += q0 + o.x;
-      dxp[a.N] += q1 + o.y;
-      dxp[2 * (size_t)a.N] += q2 + o.z;
+      dxp[0] = d0 + (q0 + o.x);    // += : the trunk's gradient is there already
+      dxp[a.N] = d1 + (q1 + o.y);
+      dxp[2 * (size_t)a.N] = d2 + (q2 + o.z);
     }
     BC_STAMP(8);
     return;
@@ -411,8 +447,10 @@ __device__ __forceinline__ void wide_bwd_conv_body(const WideBwdArgs& a) {
   BC_STAMP(8);
 }
 
+// (held at 64 registers like the first-layer form below: with the rows and fragments in flight the allocator would take
+//  74-76, seven waves per SIMD = three workgroups per CU)
 template <int TAPS, bool PRE>
-__global__ __launch_bounds__(BW2_THREADS) void wide_bwd_conv_kernel(WideBwdArgs a) {
+__global__ __launch_bounds__(BW2_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void wide_bwd_conv_kernel(WideBwdArgs a) {
   wide_bwd_conv_body<TAPS, false, PRE>(a);
 }
 // the first-layer form: its epilogue would take 72-74 registers (seven waves per SIMD = three workgroups per CU); held at 64
