@@ -138,7 +138,9 @@ SIGNATURES = {
     "geoa3_repulsion_loss_grad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, vp, vp, vp, vp]),
     "geoa3_displacement_loss": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     "geoa3_displacement_loss_grad": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "geoa3_corr_normal_loss_grad": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "geoa3_reg_fold": (C.c_int, [vp, vp, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp]),
+    "geoa3_reg_fold_points": (C.c_int, [vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
     "geoa3_knn_normal": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_local_frames": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_perp_jitter": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),
@@ -188,7 +190,7 @@ _lib = None
 
 ENOSUPPORT = -3   # GEOA3_ENOSUPPORT
 PN2_CONTRACT = 1   # GEOA3_PN2_CONTRACT
-ABI_VERSION = 607  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
+ABI_VERSION = 608  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
 
 
 class Geoa3Error(RuntimeError):

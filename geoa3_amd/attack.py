@@ -188,6 +188,54 @@ class AttackRunner:
                 t["ks_knn"] = [torch.zeros(b, ne, self.ks + 1, **i32) for _ in range(2)]
                 t["ks_knn_d"] = z(b, ne, self.ks + 1)
                 t["ks_scratch"] = t["knn_scratch"] if self.use_curv else ops.knn_self_scratch(b, ne, device)
+        # --displacement_loss_weight / --repulsion_loss_weight / --corr_normal_loss_weight (extensions): the per-point
+        # regularisers of Lib/loss_utils.py:99-123 on the cloud the objective sees, each through its mean over the points
+        # (as curvature_loss reduces its own, :95).  Per row: a sharded batch needs nothing.
+        self.w_disp = float(_cfg(cfg, "displacement_loss_weight", 0.0))
+        self.w_rep = float(_cfg(cfg, "repulsion_loss_weight", 0.0))
+        self.w_cn = float(_cfg(cfg, "corr_normal_loss_weight", 0.0))
+        self.k_disp = int(_cfg(cfg, "displacement_loss_knn", 16))
+        self.k_rep = int(_cfg(cfg, "repulsion_loss_knn", 4))
+        self.k_cn = int(_cfg(cfg, "corr_normal_loss_knn", 2))
+        self.h_rep = float(_cfg(cfg, "repulsion_loss_h", 0.03))
+        for w, k, name in ((self.w_disp, self.k_disp, "displacement_loss_knn"), (self.w_rep, self.k_rep, "repulsion_loss_knn"),
+                           (self.w_cn, self.k_cn, "corr_normal_loss_knn")):
+            if w != 0 and not 1 <= k < min(ne, 64):
+                raise ValueError("%s must be in 1..%d" % (name, min(ne, 64) - 1))
+        if self.w_rep != 0 and not self.h_rep > 0:
+            raise ValueError("repulsion_loss_h must be positive")
+        if self.sub and (self.w_disp != 0 or self.w_cn != 0):
+            raise ValueError("displacement_loss_weight / corr_normal_loss_weight != 0 cannot be combined with the dense "
+                             "sub-sample path (is_subsample_opt with n > npoint): point i of the sample is not point i of "
+                             "the clean cloud")
+        if self.w_disp != 0 or self.w_rep != 0 or self.w_cn != 0:
+            self.reg_ws = ops.reg_workspace(b, ne, max(self.k_disp if self.w_disp != 0 else 1,
+                                                       self.k_rep if self.w_rep != 0 else 1,
+                                                       self.k_cn if self.w_cn != 0 else 1), device)
+        if self.w_disp != 0:
+            # the clean cloud's table, once per batch (setup()); the curvature term's own when it is wide enough
+            self.disp_share = self.use_curv and self.k_disp <= self.k
+            t["disp_out"], t["disp_grad"], t["disp_loss"] = z(b, ne), z(b, 3, ne), z(b)
+            if not self.disp_share:
+                t["disp_knn_d"], t["disp_knn"] = z(b, n, self.k_disp + 1), torch.zeros(b, n, self.k_disp + 1, **i32)
+        if self.w_rep != 0 or self.w_cn != 0:
+            # the iterate's table: the curvature term's of this iteration holds the k + 1 nearest in its first columns
+            # (cfg.reg_share_table = False: tests); otherwise ONE search of their own for both terms, double-buffered with
+            # last iteration's table as prior
+            kmax = max(self.k_rep if self.w_rep != 0 else 1, self.k_cn if self.w_cn != 0 else 1)
+            self.reg_share = self.use_curv and kmax <= self.k and bool(_cfg(cfg, "reg_share_table", True))
+            self.reg_K = (self.k if self.reg_share else kmax) + 1
+            if not self.reg_share:
+                t["reg_knn"] = [torch.zeros(b, ne, self.reg_K, **i32) for _ in range(2)]
+                t["reg_knn_d"] = z(b, ne, self.reg_K)
+                t["reg_scratch"] = t["knn_scratch"] if self.use_curv else ops.knn_self_scratch(b, ne, device)
+        if self.w_rep != 0:
+            t["rep_out"], t["rep_grad"], t["rep_loss"] = z(b, ne), z(b, 3, ne), z(b)
+        if self.w_cn != 0:
+            # corresponding_normal_loss = geoa3_kappa with the point's own normal (a table of exactly k + 1 columns); its
+            # gradient = geoa3_corr_normal_loss_grad, pair terms in double
+            t["cn_out"], t["cn_grad"], t["cn_loss"] = z(b, ne), z(b, 3, ne), z(b)
+            t["cn_knn"] = torch.zeros(b, ne, self.k_cn + 1, **i32)   # the table's first k + 1 columns, inside the cloud
         if self.native:
             bw = b * self.eval_num if self.sub else b
             nbytes = (self.lib.geoa3_pn2ssg_workspace_bytes(bw, ne) if self.ssg
@@ -232,8 +280,9 @@ class AttackRunner:
         t["best_bs"].fill_(-1)
         self.kappa_ori = None
         self.nn1_seeded = False
+        knn_ori_d = knn_ori = None
         if self.use_curv:  # _get_kappa_ori once per batch (geoA3_attack.py:216-217)
-            _, knn_ori = ops.knn_planar(self.ori, self.ori, self.k + 1)
+            knn_ori_d, knn_ori = ops.knn_planar(self.ori, self.ori, self.k + 1)
             self.kappa_ori = ops.kappa(self.ori, self.nrm, knn_ori)
             self.knn_cur = 0
             self.knn_seeded = not self.sub
@@ -244,6 +293,17 @@ class AttackRunner:
             self.ks_seeded = not self.sub
             if self.ks_seeded:
                 t["ks_knn"][0].copy_(ops.knn_planar(self.ori, self.ori, self.ks + 1)[1])
+        if self.w_disp != 0:   # displacement_loss reads the CLEAN cloud's neighbours (Lib/loss_utils.py:101): once per batch
+            if self.disp_share:
+                self.disp_table = (knn_ori_d, knn_ori, self.k + 1)
+            else:
+                ops.knn_planar(self.ori, self.ori, self.k_disp + 1, out=(t["disp_knn_d"], t["disp_knn"]))
+                self.disp_table = (t["disp_knn_d"], t["disp_knn"], self.k_disp + 1)
+        if (self.w_rep != 0 or self.w_cn != 0) and not self.reg_share:   # the prior of the two terms' own search
+            self.reg_cur = 0
+            self.reg_seeded = not self.sub
+            if self.reg_seeded:
+                t["reg_knn"][0].copy_(ops.knn_planar(self.ori, self.ori, self.reg_K)[1])
         cls_type = {"None": 0, "CE": 1, "Margin": 2}[cfg.cls_loss_type]
         self.state = AttackState(
             B=self.b, N=self.n, classes=self.classes, targeted=int(self.targeted), cls_loss_type=cls_type,
@@ -450,6 +510,55 @@ class AttackRunner:
                 ops.reg_fold(t["ks_loss"], t["ks_grad"], self.w_knn, self.b, ne, constrain=constrain, constrain_add=geo_on,
                              g=t["g_geo"], g_add=geo_on, stream=sg)
                 geo_on = True
+            # the per-point regularisers, folded in a fixed order (displacement, repulsion, normal) through their row means:
+            # constrain_b (+)= w mean_i out[b,i], g_geo (+)= (w / ne) d(sum_i out[b,i])/dx, UN-scaled like the kNN term's
+            folds = []
+            if self.w_disp != 0:
+                tb = (self.disp_table[0].data_ptr(), self.disp_table[1].data_ptr(), self.disp_table[2])
+                ws = self.reg_ws.data_ptr()
+                check(lib.geoa3_displacement_loss(xe.data_ptr(), self.ori.data_ptr(), self.b, ne, self.k_disp, *tb,
+                                                  t["disp_out"].data_ptr(), ws, sg), "displacement_loss")
+                check(lib.geoa3_displacement_loss_grad(xe.data_ptr(), self.ori.data_ptr(), self.b, ne, self.k_disp, *tb,
+                                                       None, t["disp_grad"].data_ptr(), ws, sg), "displacement_loss_grad")
+                folds.append(("disp", self.w_disp))
+            if self.w_rep != 0 or self.w_cn != 0:
+                if self.reg_share:
+                    reg_d, reg_i = t["knn_d"], knn_adv
+                else:
+                    prior, reg_i = t["reg_knn"][self.reg_cur], t["reg_knn"][1 - self.reg_cur]
+                    check(lib.geoa3_knn_self(xe.data_ptr(), self.b, ne, self.reg_K,
+                                             prior.data_ptr() if self.reg_seeded else None, t["reg_knn_d"].data_ptr(),
+                                             reg_i.data_ptr(), t["reg_scratch"].data_ptr(), 0, sg), "knn_self")
+                    self.reg_seeded = True
+                    self.reg_cur = 1 - self.reg_cur
+                    reg_d = t["reg_knn_d"]
+            if self.w_rep != 0:
+                tb = (reg_d.data_ptr(), reg_i.data_ptr(), self.reg_K)
+                ws = self.reg_ws.data_ptr()
+                check(lib.geoa3_repulsion_loss(xe.data_ptr(), self.b, ne, self.k_rep, self.h_rep, *tb,
+                                               t["rep_out"].data_ptr(), ws, sg), "repulsion_loss")
+                check(lib.geoa3_repulsion_loss_grad(xe.data_ptr(), self.b, ne, self.k_rep, self.h_rep, *tb, None,
+                                                    t["rep_grad"].data_ptr(), ws, sg), "repulsion_loss_grad")
+                folds.append(("rep", self.w_rep))
+            if self.w_cn != 0:
+                # geoa3_kappa takes a table of exactly k + 1 columns and does not look at an index before it follows it: the
+                # columns are copied with every index brought inside the cloud (a point with a non-finite coordinate has
+                # no neighbours, index -1; its own term is NaN, and so is the row's mean).  The gradient kernel reads the
+                # table itself and refuses such a row whole.
+                torch.clamp(reg_i[:, :, :self.k_cn + 1], 0, ne - 1, out=t["cn_knn"])
+                check(lib.geoa3_kappa(xe.data_ptr(), self.nrm.data_ptr(), t["cn_knn"].data_ptr(), None, self.b, ne, ne,
+                                      self.k_cn, t["cn_out"].data_ptr(), sg), "kappa")
+                check(lib.geoa3_corr_normal_loss_grad(xe.data_ptr(), self.nrm.data_ptr(), self.b, ne, self.k_cn,
+                                                      reg_d.data_ptr(), reg_i.data_ptr(), self.reg_K, None,
+                                                      t["cn_grad"].data_ptr(), self.reg_ws.data_ptr(), sg),
+                      "corr_normal_loss_grad")
+                folds.append(("cn", self.w_cn))
+            for name, w in folds:
+                ops.reg_fold_points(t[name + "_out"], t[name + "_grad"], w, self.b, ne, term=t[name + "_loss"],
+                                    constrain=self.geo_out["constrain"], constrain_add=geo_on, g=t["g_geo"], g_add=geo_on,
+                                    stream=sg)
+                constrain = self.geo_out["constrain"]
+                geo_on = True
             if self.w_uni != 0:   # constrain (+)= w U before the head reads it (no other term on: constrain = w U)
                 ops.uniform_loss(xe, contract=self.uni_contract, workspace=self.uni_ws, out=(t["uni_loss"], t["uni_grad"]))
                 constrain = self.geo_out["constrain"]
@@ -541,6 +650,13 @@ class AttackRunner:
                                            t["offset"].data_ptr(), x.data_ptr(), self.b, self.n,
                                            float(_cfg(cfg, "cc_linf", 0.0)), s), "attack_project")
 
+    @property
+    def knn_searches_per_iteration(self) -> int:
+        """geoa3_knn_self launches of one objective(): the curvature term's, the kNN-smoothing term's own and the ONE the
+        repulsion and normal terms share when the curvature term's table does not serve them."""
+        return (int(self.use_curv) + int(self.w_knn != 0 and not self.knn_share) +
+                int((self.w_rep != 0 or self.w_cn != 0) and not self.reg_share))
+
     def end_search_step(self, sync_last_label: Optional[Callable[[Tensor], None]] = None):
         if sync_last_label is not None:
             sync_last_label(self.t["last_label"])
@@ -551,11 +667,14 @@ class AttackRunner:
     def info_line(self, search_step, step, i, loader_len) -> str:
         """The reference's progress line (geoA3_attack.py:129,138,154,163,365); the ONLY host sync in the loop."""
         cfg, t = self.cfg, self.t
+        regs = ((self.w_disp, "disp_loss", "disp_loss"), (self.w_rep, "rep_loss", "rep_loss"),
+                (self.w_cn, "cn_loss", "cnor_loss"))
         vals = torch.stack([t["loss_n"].mean() * (self.b / float(self.global_batch)), t["cls_loss"].mean(),
                             self.geo_out["dis_loss"].mean(), self.geo_out["hd_loss"].mean(),
                             self.geo_out["curv_loss"].mean()] +
                            ([self.t["uni_loss"]] if self.w_uni != 0 else []) +
-                           ([self.t["ks_loss"].mean()] if self.w_knn != 0 else [])).tolist()
+                           ([self.t["ks_loss"].mean()] if self.w_knn != 0 else []) +
+                           [self.t[name].mean() for w, name, _ in regs if w != 0]).tolist()
         info = "[{5}/{6}][{0}/{1}][{2}/{3}] \t loss: {4:6.4f}\t".format(
             search_step + 1, cfg.binary_max_steps, step + 1, cfg.iter_max_steps, vals[0], i, loader_len)
         info += "cls_loss: {0:6.4f}\t".format(vals[1])
@@ -569,8 +688,14 @@ class AttackRunner:
             info += "curv_loss : {0:6.4f}\t".format(vals[4])
         if self.w_uni != 0:
             info += "uniform : {0:6.4f}\t".format(vals[5])
+        pos = 5 + int(self.w_uni != 0)
         if self.w_knn != 0:
-            info += "knn_smooth : {0:6.4f}\t".format(vals[-1])
+            info += "knn_smooth : {0:6.4f}\t".format(vals[pos])
+            pos += 1
+        for w, _, label in regs:
+            if w != 0:
+                info += "{0} : {1:6.4f}\t".format(label, vals[pos])
+                pos += 1
         return info
 
     def run(self, init_offsets: Optional[Sequence[Tensor]] = None, i: int = 0, loader_len: int = 1,
@@ -624,7 +749,9 @@ RUNNER_CFG_FIELDS = ("attack_label", "iter_max_steps", "curv_loss_knn", "curv_lo
                      "knn_range", "is_subsample_opt", "eval_num", "is_pre_jitter_input", "is_pro_grad",
                      "brute_force_nn1", "classes", "deterministic", "late_join", "knn_method",
                      "is_use_knn_smoothing_loss", "knn_smoothing_loss_weight", "knn_smoothing_k", "knn_threshold_coef",
-                     "knn_smoothing_share_table")
+                     "knn_smoothing_share_table", "displacement_loss_weight", "displacement_loss_knn",
+                     "repulsion_loss_weight", "repulsion_loss_knn", "repulsion_loss_h", "corr_normal_loss_weight",
+                     "corr_normal_loss_knn", "reg_share_table")
 
 
 def unpack_input(input_data, targeted: bool):

@@ -1,7 +1,9 @@
 // The neighbour-based regularisers of the reference's Lib/loss_utils.py that are functions of a self K-NN table:
 //   kNN_smoothing_loss (:135-149), repulsion_loss (:119-123), displacement_loss (:99-107),
-// each as a forward and a backward entry point, and the fold of w * S into the attack's constrain loss and gradient.
-// (corresponding_normal_loss, :109-117, is geoa3_kappa + the dkappa path of geoa3_geo_loss_grad: no kernel here.)
+// each as a forward and a backward entry point, and the fold of w * S into the attack's constrain loss and gradient
+// (geoa3_reg_fold: a per-row term; geoa3_reg_fold_points: a per-point term through its row mean).
+// corresponding_normal_loss (:109-117): the forward is geoa3_kappa with the point's own normal; its backward is a mode of
+// reg_bwd_kernel here (pair terms in double; the dkappa path of geoa3_geo_loss_grad is the float32 alternative).
 //
 // The table is geoa3_knn_self's: dists / idx [B,N,ld] ascending by (distance, index), column 0 dropped as the reference's
 // [:, :, 1:].  The caller hands it over (knn_d, knn_i, knn_ld >= k + 1: the first k + 1 columns of a wider table serve)
@@ -29,7 +31,8 @@ constexpr size_t REG_LDS_MAX = 160 * 1024 - 6144;       // dynamic LDS (the stat
 constexpr int REG_FX_BITS = 40;
 constexpr int REG_MAX_N = 8192;
 
-enum { REG_SMOOTH = 0, REG_REPULSE = 1, REG_DISPLACE = 2 };
+enum { REG_SMOOTH = 0, REG_REPULSE = 1, REG_DISPLACE = 2, REG_NORMAL = 3 };
+constexpr double REG_NORM_EPS = 1e-12;                  // Lib/utility.py:30 (_normalize eps)
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(REG_T) void displace_fwd_kernel(const float* __rest
 
 struct RegBwd {
   const float* pc;         // the cloud the gradient is taken at (displacement_loss: adv)
-  const float* ori;        // displacement_loss only
+  const float* ori;        // displacement_loss: the clean cloud; corresponding_normal_loss: the normals [B,3,N]
   const float* knn_d;      // [B,N,ld]
   const int32_t* knn_i;    // [B,N,ld]
   const float* g;          // upstream gradient: [B] (kNN_smoothing_loss) / [B,N]; NULL = ones
@@ -182,7 +185,7 @@ struct RegBwd {
 
 // LDS: [sums NA x N int64 (LDS)] [x y z, N floats each (LDS, not displacement)] [aux]
 //   aux of kNN_smoothing_loss: the mask, N bytes (s_i, N floats, sits in the sums' space before they are cleared; !LDS: in
-//   front of the mask); of displacement_loss: theta, N floats
+//   front of the mask); of displacement_loss: theta, N doubles
 template <int MODE, bool LDS>
 __global__ __launch_bounds__(REG_T) void reg_bwd_kernel(RegBwd p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(REG_T) void reg_bwd_kernel(RegBwd p) {
   float* s_s = LDS ? reinterpret_cast<float*>(s_raw) : reinterpret_cast<float*>(q);   // (kNN_smoothing_loss)
   if (MODE == REG_SMOOTH && !LDS) q += (size_t)N * sizeof(float);
   unsigned char* s_c = q;                               // (kNN_smoothing_loss)
-  float* s_th = reinterpret_cast<float*>(q);            // (displacement_loss)
+  double* s_th = reinterpret_cast<double*>(q);          // (displacement_loss: theta in double, its differences cancel)
   const float* D = p.knn_d + (size_t)b * N * ld;
   const int32_t* I = p.knn_i + (size_t)b * N * ld;
   float* G = p.grad + (size_t)b * 3 * N;
@@ -208,9 +211,11 @@ __global__ __launch_bounds__(REG_T) void reg_bwd_kernel(RegBwd p) {
   if (MODE == REG_DISPLACE) {
     const float* O = p.ori + (size_t)b * 3 * N;
     for (int i = tid; i < N; i += REG_T) {
-      const float th = geoa3_sqdist(X[i], X[N + i], X[2 * N + i], O[i], O[N + i], O[2 * N + i]);
+      const double dx = (double)X[i] - (double)O[i], dy = (double)X[N + i] - (double)O[N + i],
+                   dz = (double)X[2 * N + i] - (double)O[2 * N + i];
+      const double th = dx * dx + dy * dy + dz * dz;
       s_th[i] = th;
-      bad = bad || geoa3_nonfinite(th);
+      bad = bad || geoa3_nonfinite((float)th);           // (NaN, infinite, or beyond what the forward's float theta holds)
     }
   } else {
     for (int i = tid; i < 3 * N; i += REG_T) {
@@ -243,22 +248,42 @@ __global__ __launch_bounds__(REG_T) void reg_bwd_kernel(RegBwd p) {
     const int m = e - i * k + 1;
     j = I[(size_t)i * ld + m];
     if ((unsigned)j >= (unsigned)N) return false;
-    double w;
-    if (MODE == REG_SMOOTH) {
-      w = s_c[i] ? gb : 0.0;
-    } else if (MODE == REG_REPULSE) {
-      const double d = (double)D[(size_t)i * ld + m];
-      const double u = (d * d) / h2;
-      w = (double)(gp ? gp[i] : 1.f) * (-(1.0 / kd)) * exp(-u) * (1.0 - 2.0 * u);
-    } else {
-      t0 = (2.0 / kd) * ((double)s_th[j] - (double)s_th[i]) * (double)(gp ? gp[i] : 1.f);
+    if (MODE == REG_DISPLACE) {
+      t0 = (2.0 / kd) * (s_th[j] - s_th[i]) * (double)(gp ? gp[i] : 1.f);
       t1 = t2 = 0.0;
       return true;
     }
+    const double dx = (double)cx[i] - (double)cx[j], dy = (double)cx[N + i] - (double)cx[N + j],
+                 dz = (double)cx[2 * N + i] - (double)cx[2 * N + j];
+    if (MODE == REG_NORMAL) {
+      // out_i = mean_m |t|, t = <v / max(|v|, eps), n_i>, v = x_j - x_i:  d|t|/dx_j = sign(t) (n_i - t v^) / |v| (|v| > eps;
+      // sign(0) = 0 as torch.abs's backward), and the opposite on x_i -- the term ADDED to point i
+      const float* Nm = p.ori + (size_t)b * 3 * N;
+      const double nx = (double)Nm[i], ny = (double)Nm[N + i], nz = (double)Nm[2 * N + i];
+      const double r = sqrt(dx * dx + dy * dy + dz * dz);
+      const double inv = 1.0 / fmax(r, REG_NORM_EPS);
+      const double ux = -dx * inv, uy = -dy * inv, uz = -dz * inv;       // v^
+      const double t = ux * nx + uy * ny + uz * nz;
+      const double sg = t > 0.0 ? 1.0 : (t < 0.0 ? -1.0 : 0.0);
+      const double c = -(sg * inv / kd) * (double)(gp ? gp[i] : 1.f);
+      const double tt = r > REG_NORM_EPS ? t : 0.0;                       // (clamped length: v^ = v / eps is linear in v)
+      t0 = c * (nx - tt * ux);
+      t1 = c * (ny - tt * uy);
+      t2 = c * (nz - tt * uz);
+      return true;                                        // (a NaN normal gives NaN terms: the instance is refused below)
+    }
+    double w;
+    if (MODE == REG_SMOOTH) {
+      w = s_c[i] ? gb : 0.0;
+    } else {                                              // (repulsion: the squared distance again in double, from the cloud)
+      const double d = dx * dx + dy * dy + dz * dz;
+      const double u = (d * d) / h2;
+      w = (double)(gp ? gp[i] : 1.f) * (-(1.0 / kd)) * exp(-u) * (1.0 - 2.0 * u);
+    }
     const double w2 = 2.0 * w;
-    t0 = w2 * ((double)cx[i] - (double)cx[j]);
-    t1 = w2 * ((double)cx[N + i] - (double)cx[N + j]);
-    t2 = w2 * ((double)cx[2 * N + i] - (double)cx[2 * N + j]);
+    t0 = w2 * dx;
+    t1 = w2 * dy;
+    t2 = w2 * dz;
     return true;
   };
 
@@ -333,8 +358,56 @@ __global__ __launch_bounds__(256) void reg_fold_kernel(const float* __restrict__
   }
 }
 
+// A per-point term out [B,N] through its row mean: one workgroup per row.  The mean is summed in double as block_sum
+// does (thread t takes points t, t + 512, ...: the order depends on N only) and rounded to float once; w * term and
+// (w / N) * grad are formed and added in double and rounded once.  A NaN mean (a non-finite coordinate upstream) makes the
+// row's whole g NaN, whatever grad holds: "a NaN row stays NaN".  VEC: rows of g / grad are float4-addressable.
+template <bool VEC>
+__global__ __launch_bounds__(REG_T) void reg_fold_points_kernel(const float* __restrict__ out, const float* __restrict__ grad,
+                                                                float w, int N, float* __restrict__ term,
+                                                                float* __restrict__ constrain, int constrain_add,
+                                                                float* __restrict__ g, int g_add) {
+  __shared__ double s_red[REG_T];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  bool nan_row = false;
+  if (out) {
+    const float* O = out + (size_t)b * N;
+    double v = 0.0;
+    for (int i = tid; i < N; i += REG_T) v += (double)O[i];
+    const float mean = (float)(block_sum(v, s_red) / (double)N);
+    nan_row = mean != mean;
+    if (tid == 0) {
+      if (term) term[b] = mean;
+      if (constrain) constrain[b] = (float)((constrain_add ? (double)constrain[b] : 0.0) + (double)w * (double)mean);
+    }
+  }
+  if (!g) return;
+  const double wn = (double)w / (double)N;
+  const float qnan = __builtin_nanf("");
+  const float* S = grad + (size_t)b * 3 * N;
+  float* G = g + (size_t)b * 3 * N;
+  auto fold = [&](float gv, float sv) -> float {
+    return nan_row ? qnan : (float)((g_add ? (double)gv : 0.0) + wn * (double)sv);
+  };
+  if (VEC) {
+    const float4* S4 = reinterpret_cast<const float4*>(S);
+    float4* G4 = reinterpret_cast<float4*>(G);
+    for (int i = tid; i < 3 * (N / 4); i += REG_T) {
+      const float4 s = S4[i];
+      float4 r = g_add ? G4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      r.x = fold(r.x, s.x);
+      r.y = fold(r.y, s.y);
+      r.z = fold(r.z, s.z);
+      r.w = fold(r.w, s.w);
+      G4[i] = r;
+    }
+  } else {
+    for (int i = tid; i < 3 * N; i += REG_T) G[i] = fold(g_add ? G[i] : 0.f, S[i]);
+  }
+}
+
 size_t reg_lds_bwd(int mode, int N) {   // dynamic LDS of the LDS form
-  if (mode == REG_DISPLACE) return (size_t)N * 12;
+  if (mode == REG_DISPLACE) return (size_t)N * 16;
   return (size_t)N * (mode == REG_SMOOTH ? 37 : 36);
 }
 
@@ -454,6 +527,18 @@ extern "C" int geoa3_repulsion_loss_grad(const float* pc, int B, int N, int k, f
   return launch_reg_bwd<REG_REPULSE>(p, B, workspace, geoa3_stream(stream));
 }
 
+extern "C" int geoa3_corr_normal_loss_grad(const float* pc, const float* normal, int B, int N, int k, const float* knn_d,
+                                           const int32_t* knn_i, int knn_ld, const float* g, float* grad, void* workspace,
+                                           void* stream) {
+  if (!pc || !normal || !grad) return GEOA3_EINVAL;
+  int rc = reg_check(B, N, k);
+  if (rc != GEOA3_OK) return rc;
+  rc = reg_table(pc, B, N, k, &knn_d, &knn_i, &knn_ld, workspace, stream);
+  if (rc != GEOA3_OK) return rc;
+  RegBwd p = {pc, normal, knn_d, knn_i, g, grad, nullptr, N, k, knn_ld, 0.f, 0.f};
+  return launch_reg_bwd<REG_NORMAL>(p, B, workspace, geoa3_stream(stream));
+}
+
 extern "C" int geoa3_displacement_loss(const float* adv, const float* ori, int B, int N, int k, const float* knn_d,
                                        const int32_t* knn_i, int knn_ld, float* out, void* workspace, void* stream) {
   if (!adv || !ori || !out) return GEOA3_EINVAL;
@@ -488,6 +573,18 @@ extern "C" int geoa3_reg_fold(const float* loss, const float* grad, float w, int
   if (blocks > 2048 && (size_t)B <= 2048 * 256) blocks = 2048;
   hipLaunchKernelGGL(reg_fold_kernel, dim3((unsigned)blocks), dim3(256), 0, geoa3_stream(stream), loss, grad, w, B, total,
                      constrain, constrain_add, g, g_add);
+  GEOA3_CHECK_LAUNCH();
+  return GEOA3_OK;
+}
+
+extern "C" int geoa3_reg_fold_points(const float* out, const float* grad, float w, int B, int N, float* term,
+                                     float* constrain, int constrain_add, float* g, int g_add, void* stream) {
+  if (B <= 0 || N <= 0 || (!term && !constrain && !g) || ((term || constrain) && !out) || (g && !grad)) return GEOA3_EINVAL;
+  if (N > (1 << 28)) return GEOA3_ENOSUPPORT;           // (3 N stays an int)
+  const bool vec = g && N % 4 == 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
+  auto kern = vec ? reg_fold_points_kernel<true> : reg_fold_points_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(REG_T), 0, geoa3_stream(stream), out, grad, w, N, term, constrain,
+                     constrain_add, g, g_add);
   GEOA3_CHECK_LAUNCH();
   return GEOA3_OK;
 }

@@ -358,12 +358,43 @@ def corresponding_normal_loss_grad(adv: Tensor, normal: Tensor, knn_idx: Tensor,
     return torch.where(_instance_bad(adv).view(B, 1, 1), o["grad"].new_full((), float("nan")), o["grad"])
 
 
+def corr_normal_loss_grad(pc: Tensor, normal: Tensor, k: int = 2, g: Optional[Tensor] = None, knn=None,
+                          workspace: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """geoa3_corr_normal_loss_grad: d (sum g . corresponding_normal_loss) / d pc [B,3,N] with every pair term formed in
+    double (g [B,N]; None = ones); the attack loop's gradient of the term."""
+    B, _, N = pc.shape
+    if tuple(normal.shape) != (B, 3, N):
+        raise _lib.Geoa3Error("corr_normal_loss_grad: pc and normal must have the same shape")
+    grad = out if out is not None else torch.empty(B, 3, N, device=pc.device, dtype=torch.float32)
+    d, i, ld = _reg_table(knn, B, N, int(k))
+    check(_lib.load().geoa3_corr_normal_loss_grad(_p(pc, torch.float32), _p(normal, torch.float32), B, N, int(k), d, i, ld,
+                                                  _p(g, torch.float32), _p(grad, torch.float32),
+                                                  _p(_reg_ws(workspace, B, N, k, pc.device)), _stream()),
+          "geoa3_corr_normal_loss_grad")
+    return grad
+
+
 def reg_fold(loss: Optional[Tensor], grad: Optional[Tensor], w: float, B: int, N: int, constrain: Optional[Tensor] = None,
              constrain_add: bool = False, g: Optional[Tensor] = None, g_add: bool = False,
              stream: Optional[int] = None) -> None:
     """geoa3_reg_fold: constrain (+)= w loss [B]; g (+)= w grad [B,3,N]."""
     check(_lib.load().geoa3_reg_fold(_p(loss), _p(grad), float(w), B, N, _p(constrain), int(constrain_add), _p(g),
                                      int(g_add), _stream() if stream is None else stream), "geoa3_reg_fold")
+
+
+def reg_fold_points(out: Optional[Tensor], grad: Optional[Tensor], w: float, B: int, N: int, term: Optional[Tensor] = None,
+                    constrain: Optional[Tensor] = None, constrain_add: bool = False, g: Optional[Tensor] = None,
+                    g_add: bool = False, stream: Optional[int] = None) -> None:
+    """geoa3_reg_fold_points: term [B] = mean_i out [B,N]; constrain (+)= w term; g (+)= (w / N) grad [B,3,N], grad being
+    d (sum_i out) / d cloud (the *_grad entry points with g = None)."""
+    for name, x, numel in (("out", out, B * N), ("grad", grad, B * 3 * N), ("term", term, B), ("constrain", constrain, B),
+                           ("g", g, B * 3 * N)):
+        if x is not None and x.numel() != numel:
+            raise _lib.Geoa3Error("reg_fold_points: %s holds %d elements, expected %d" % (name, x.numel(), numel))
+    check(_lib.load().geoa3_reg_fold_points(_p(out, torch.float32), _p(grad, torch.float32), float(w), B, N,
+                                            _p(term, torch.float32), _p(constrain, torch.float32), int(constrain_add),
+                                            _p(g, torch.float32), int(g_add), _stream() if stream is None else stream),
+          "geoa3_reg_fold_points")
 
 
 # ---------------------------------------------------------------------------------------------

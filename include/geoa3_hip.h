@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 607
+#define GEOA3_ABI_VERSION 608
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -628,7 +628,8 @@ int geoa3_knn_smoothing_loss_grad(const float* pc, int B, int N, int k, float co
                                   void* stream);
 /* repulsion_loss, Lib/loss_utils.py:119-123: out[b,i] = -mean_m d exp(-d^2 / h^2), d the SQUARED distance, squared again
  * inside the exponent as the reference writes it.  Gradient (g [B,N]): pair coefficient
- * -(1/k) exp(-d^2/h^2) (1 - 2 d^2/h^2) g_i on 2 (x_i - x_j). */
+ * -(1/k) exp(-d^2/h^2) (1 - 2 d^2/h^2) g_i on 2 (x_i - x_j), d formed again in double from the cloud (the table gives the
+ * neighbours; its float32 distances are the forward's). */
 int geoa3_repulsion_loss(const float* pc, int B, int N, int k, float h, const float* knn_d, const int32_t* knn_i,
                          int knn_ld, float* out, void* workspace, void* stream);
 int geoa3_repulsion_loss_grad(const float* pc, int B, int N, int k, float h, const float* knn_d, const int32_t* knn_i,
@@ -640,12 +641,28 @@ int geoa3_displacement_loss(const float* adv, const float* ori, int B, int N, in
 int geoa3_displacement_loss_grad(const float* adv, const float* ori, int B, int N, int k, const float* knn_d,
                                  const int32_t* knn_i, int knn_ld, const float* g, float* grad, void* workspace,
                                  void* stream);
-/* (corresponding_normal_loss, Lib/loss_utils.py:109-117, is geoa3_knn_self + geoa3_kappa with nn_idx = NULL; its gradient
- * is the dkappa path of geoa3_geo_loss_grad with the identity as i_ao.) */
+/* corresponding_normal_loss, Lib/loss_utils.py:109-117: the forward is geoa3_knn_self + geoa3_kappa with nn_idx = NULL.
+ * Gradient (g [B,N]; normal [B,3,N], read by index: point i, normal i) with the conventions of the *_grad entry points
+ * above: pair (i, j) adds -g_i / k * sign(t) (n_i - t v^) / |v| to point i and subtracts it from point j, v = x_j - x_i,
+ * v^ = v / max(|v|, 1e-12), t = <v^, n_i>, sign(0) = 0, every pair term formed in double.  (The dkappa path of
+ * geoa3_geo_loss_grad with the identity as i_ao gives the same gradient from float32 pair terms.) */
+int geoa3_corr_normal_loss_grad(const float* pc, const float* normal, int B, int N, int k, const float* knn_d,
+                                const int32_t* knn_i, int knn_ld, const float* g, float* grad, void* workspace,
+                                void* stream);
 /* A per-row term S [B] with gradient dS [B,3,N] joins the attack's constrain loss (--is_use_knn_smoothing_loss):
  * constrain [B] (optional) = (constrain_add ? constrain : 0) + w * loss;  g [B,3,N] (optional) = (g_add ? g : 0) + w * grad. */
 int geoa3_reg_fold(const float* loss, const float* grad, float w, int B, int N, float* constrain, int constrain_add,
                    float* g, int g_add, void* stream);
+/* A per-point term out [B,N] joins the constrain loss through its row mean (Lib/loss_utils.py:95):
+ *   term[b]      (optional) = mean_i out[b,i], accumulated in double in an order that depends on N only;
+ *   constrain[b] (optional) = (constrain_add ? constrain[b] : 0) + w * term[b];
+ *   g [B,3,N]    (optional) = (g_add ? g : 0) + (w / N) * grad,
+ *                grad = d(sum_i out[b,i]) / d cloud, what the *_grad entry points write with g = NULL.
+ * One launch, one workgroup per row: a row reads nothing outside itself, repeated calls are bit identical.  Sums and
+ * products are formed in double and rounded to float once.  A row whose mean is NaN gets NaN in all of its g, whatever
+ * grad holds.  out may be NULL when only g is wanted, grad when g is not (GEOA3_EINVAL when nothing is asked for). */
+int geoa3_reg_fold_points(const float* out, const float* grad, float w, int B, int N, float* term, float* constrain,
+                          int constrain_add, float* g, int g_add, void* stream);
 
 #ifdef __cplusplus
 }

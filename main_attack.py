@@ -82,6 +82,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--is_use_knn_smoothing_loss", action="store_true", default=False,
                    help="add knn_smoothing_loss_weight * kNN_smoothing_loss(knn_smoothing_k, knn_threshold_coef) to the "
                         "constrain loss (the reference parses the three flags and never reads them)")
+    p.add_argument("--displacement_loss_weight", type=float, default=0.0,
+                   help="add w * mean_i displacement_loss(adv, ori, displacement_loss_knn) to the constrain loss")
+    p.add_argument("--displacement_loss_knn", type=int, default=16)
+    p.add_argument("--repulsion_loss_weight", type=float, default=0.0,
+                   help="add w * mean_i repulsion_loss(adv, repulsion_loss_knn, repulsion_loss_h) to the constrain loss")
+    p.add_argument("--repulsion_loss_knn", type=int, default=4)
+    p.add_argument("--repulsion_loss_h", type=float, default=0.03)
+    p.add_argument("--corr_normal_loss_weight", type=float, default=0.0,
+                   help="add w * mean_i corresponding_normal_loss(adv, normal, corr_normal_loss_knn) to the constrain loss")
+    p.add_argument("--corr_normal_loss_knn", type=int, default=2)
     p.add_argument("--out_root", default="Exps", type=str, help="root of the output tree (reference: Exps)")
     p.add_argument("--quiet", action="store_true", default=False)
     p.add_argument("--synthetic_npoint", type=int, default=0,
@@ -114,6 +124,14 @@ def saved_dir_name(cfg) -> str:
             (getattr(cfg, "is_use_knn_smoothing_loss", False),
              "_kNNSmooth" + str(cfg.knn_smoothing_loss_weight) + "_k" + str(cfg.knn_smoothing_k) + "_coef" +
              str(cfg.knn_threshold_coef)),
+            (getattr(cfg, "displacement_loss_weight", 0.0) != 0,
+             "_Disp" + str(getattr(cfg, "displacement_loss_weight", 0.0)) + "_k" + str(getattr(cfg, "displacement_loss_knn", 16))),
+            (getattr(cfg, "repulsion_loss_weight", 0.0) != 0,
+             "_Rep" + str(getattr(cfg, "repulsion_loss_weight", 0.0)) + "_k" + str(getattr(cfg, "repulsion_loss_knn", 4)) +
+             "_h" + str(getattr(cfg, "repulsion_loss_h", 0.03))),
+            (getattr(cfg, "corr_normal_loss_weight", 0.0) != 0,
+             "_CorrNor" + str(getattr(cfg, "corr_normal_loss_weight", 0.0)) + "_k" +
+             str(getattr(cfg, "corr_normal_loss_knn", 2))),
         ]
         for cond, suffix in optional:
             if cond:
