@@ -143,6 +143,8 @@ SIGNATURES = {
     "geoa3_reg_fold_points": (C.c_int, [vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
     "geoa3_knn_normal": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_local_frames": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_estimate_normal": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_normalize_cloud": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_perp_jitter": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),
     "geoa3_smoothness": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_sor_statistic": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),

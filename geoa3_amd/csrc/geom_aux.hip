@@ -1,6 +1,7 @@
 // Geometry helpers of the dense-cloud attack path, the point-removal defence and the smoothness measurement
 // (gfx950).  Reference: Lib/utility.py:91-108 (estimate_normal_via_ori_normal), :116-149 (estimate_perpendicular),
-// :175-187 (farthest_points_sample); defense.py:18-45; Measurement/compute_data_smoothness.py:37-67.
+// :175-187 (farthest_points_sample); defense.py:18-45; Measurement/compute_data_smoothness.py:37-67; and of the input
+// side: Lib/utility.py:40-89 (estimate_normal), Provider/modelnet10_instance250.py:120-124 (the re-sampling's tail).
 // All of them sit on top of the K-NN kernels of geom_nn.hip; the reference runs them as chains of dense torch ops
 // (an [n,n] distance matrix per cloud, per-point numpy eig loops, python loops over instances).
 #include "common.h"
@@ -228,13 +229,16 @@ __device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq
   a = c * vp2 - s * vq2; bb = s * vp2 + c * vq2; vp2 = a; vq2 = bb;
 }
 
-__global__ __launch_bounds__(256) void local_frame_kernel(const float* __restrict__ pc,
-                                                          const int32_t* __restrict__ knn, int N, int K1,
-                                                          float* __restrict__ evals, float* __restrict__ evecs) {
-  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  const float* P = pc + (size_t)b * 3 * N;
-  const int32_t* nb = knn + ((size_t)b * N + i) * K1;
+// Sorted eigenpairs of one neighbourhood's covariance: w ascending, v[e][c] = component c of eigenvector e.
+struct LocalFrame {
+  double w[3];
+  double v[3][3];
+};
+
+// Mean and covariance (fp32, factor 1/(k-1)) of the points listed in columns 1..K1-1 of one table row, then the fp64
+// Jacobi: the ONE statement of the neighbourhood's frame, shared by local_frame_kernel and estimate_normal_kernel.
+__device__ __forceinline__ void local_frame_solve(const float* __restrict__ P, const int32_t* __restrict__ nb, int N,
+                                                  int K1, LocalFrame& f) {
   const int k = K1 - 1;
   float mx = 0.f, my = 0.f, mz = 0.f;
   for (int m = 1; m <= k; ++m) {
@@ -279,22 +283,183 @@ __global__ __launch_bounds__(256) void local_frame_kernel(const float* __restric
   GEOA3_SWAP_E(a11, a22, v10, v11, v12, v20, v21, v22)
   GEOA3_SWAP_E(a00, a11, v00, v01, v02, v10, v11, v12)
 #undef GEOA3_SWAP_E
+  f.w[0] = a00; f.w[1] = a11; f.w[2] = a22;
+  f.v[0][0] = v00; f.v[0][1] = v01; f.v[0][2] = v02;
+  f.v[1][0] = v10; f.v[1][1] = v11; f.v[1][2] = v12;
+  f.v[2][0] = v20; f.v[2][1] = v21; f.v[2][2] = v22;
+}
+
+// The sign that makes an eigenvector's largest-magnitude component positive (the first of equal magnitudes).
+__device__ __forceinline__ double canonical_sign(double x, double y, double z) {
+  const double ax = fabs(x), ay = fabs(y), az = fabs(z);
+  const double lead = (ax >= ay && ax >= az) ? x : (ay >= az ? y : z);
+  return lead < 0.0 ? -1.0 : 1.0;
+}
+
+__global__ __launch_bounds__(256) void local_frame_kernel(const float* __restrict__ pc,
+                                                          const int32_t* __restrict__ knn, int N, int K1,
+                                                          float* __restrict__ evals, float* __restrict__ evecs) {
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  LocalFrame f;
+  local_frame_solve(pc + (size_t)b * 3 * N, knn + ((size_t)b * N + i) * K1, N, K1, f);
   const size_t bN = (size_t)b * 3 * N;
-  evals[bN + i] = (float)a00;
-  evals[bN + N + i] = (float)a11;
-  evals[bN + 2 * N + i] = (float)a22;
+  evals[bN + i] = (float)f.w[0];
+  evals[bN + N + i] = (float)f.w[1];
+  evals[bN + 2 * N + i] = (float)f.w[2];
   float* E = evecs + (size_t)b * 9 * N;
-  auto put = [&](int e, double x, double y, double z) {
-    const double ax = fabs(x), ay = fabs(y), az = fabs(z);
-    const double lead = (ax >= ay && ax >= az) ? x : (ay >= az ? y : z);
-    const double sgn = lead < 0.0 ? -1.0 : 1.0;
-    E[(size_t)(e * 3 + 0) * N + i] = (float)(sgn * x);
-    E[(size_t)(e * 3 + 1) * N + i] = (float)(sgn * y);
-    E[(size_t)(e * 3 + 2) * N + i] = (float)(sgn * z);
+  auto put = [&](int e) {
+    const double sgn = canonical_sign(f.v[e][0], f.v[e][1], f.v[e][2]);
+    E[(size_t)(e * 3 + 0) * N + i] = (float)(sgn * f.v[e][0]);
+    E[(size_t)(e * 3 + 1) * N + i] = (float)(sgn * f.v[e][1]);
+    E[(size_t)(e * 3 + 2) * N + i] = (float)(sgn * f.v[e][2]);
   };
-  put(0, v00, v01, v02);
-  put(1, v10, v11, v12);
-  put(2, v20, v21, v22);
+  put(0);
+  put(1);
+  put(2);
+}
+
+// ------------------------------------------------------------------------------------------
+// estimate_normal (Lib/utility.py:40-89): the eigenvector of the smallest eigenvalue of local_frame_solve's frame,
+// one thread per point.  orient 0: the largest-magnitude component is positive (exactly local_frame_kernel's
+// evecs[:,0]).  orient 1 ("outward"): the sign makes n.(p_i - c) >= 0, c = the cloud's centroid; a dot product of
+// exactly 0 keeps the orient-0 sign.  (The reference's own rule, :62-64, takes the sign of n.(sum of the mean-centred
+// neighbours): that sum is zero up to rounding, so it is not mirrored.)
+// Every workgroup forms the centroid of its cloud itself, in fp64 and in ONE order (thread t adds points t, t+256, ...;
+// a butterfly inside each wavefront; the four wave sums in ascending order), so all workgroups hold the same bits and
+// no atomic or scratch buffer is needed.
+// Loud NaN: a row that lists a point with a non-finite coordinate (column 0 included) gives a NaN normal -- the
+// covariance carries it through the Jacobi, the row's own point is tested -- and under orient 1 a non-finite
+// centroid (a non-finite coordinate anywhere in the cloud) makes every normal of that cloud NaN.
+// ------------------------------------------------------------------------------------------
+constexpr int EN_T = 256;
+__global__ __launch_bounds__(EN_T) void estimate_normal_kernel(const float* __restrict__ pc,
+                                                               const int32_t* __restrict__ knn, int N, int K1,
+                                                               int orient, float* __restrict__ out) {
+  __shared__ double s_c[EN_T / GEOA3_WAVE][3];
+  const int b = blockIdx.y, tid = threadIdx.x, i = blockIdx.x * EN_T + tid;
+  const float* P = pc + (size_t)b * 3 * N;
+  double cx = 0.0, cy = 0.0, cz = 0.0;
+  if (orient) {   // (uniform over the launch)
+    for (int j = tid; j < N; j += EN_T) {
+      cx += (double)P[j];
+      cy += (double)P[N + j];
+      cz += (double)P[2 * N + j];
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      cx += __shfl_xor(cx, o, 64);
+      cy += __shfl_xor(cy, o, 64);
+      cz += __shfl_xor(cz, o, 64);
+    }
+    if ((tid & 63) == 0) {
+      s_c[tid >> 6][0] = cx;
+      s_c[tid >> 6][1] = cy;
+      s_c[tid >> 6][2] = cz;
+    }
+    __syncthreads();
+    cx = cy = cz = 0.0;
+    for (int w = 0; w < EN_T / GEOA3_WAVE; ++w) {
+      cx += s_c[w][0];
+      cy += s_c[w][1];
+      cz += s_c[w][2];
+    }
+    const double inv_n = 1.0 / (double)N;
+    cx *= inv_n;
+    cy *= inv_n;
+    cz *= inv_n;
+  }
+  if (i >= N) return;
+  const int32_t* nb = knn + ((size_t)b * N + i) * K1;
+  LocalFrame f;
+  local_frame_solve(P, nb, N, K1, f);
+  const double x = f.v[0][0], y = f.v[0][1], z = f.v[0][2];
+  double sgn = canonical_sign(x, y, z);
+  const float px = P[i], py = P[N + i], pz = P[2 * N + i];
+  const int j0 = nb[0];
+  bool bad = geoa3_nonfinite(px) || geoa3_nonfinite(py) || geoa3_nonfinite(pz) || geoa3_nonfinite(P[j0]) ||
+             geoa3_nonfinite(P[N + j0]) || geoa3_nonfinite(P[2 * N + j0]);
+  if (orient) {
+    const double d = sgn * (x * ((double)px - cx) + y * ((double)py - cy) + z * ((double)pz - cz));
+    bad = bad || !(fabs(d) < (double)INF);
+    sgn = d < 0.0 ? -sgn : sgn;
+  }
+  const float nan = __uint_as_float(0x7fc00000u);
+  float* O = out + (size_t)b * 3 * N;
+  O[i] = bad ? nan : (float)(sgn * x);
+  O[N + i] = bad ? nan : (float)(sgn * y);
+  O[2 * N + i] = bad ? nan : (float)(sgn * z);
+}
+
+// ------------------------------------------------------------------------------------------
+// The tail of the dataset's re-sampling (Provider/modelnet10_instance250.py:120-124): subtract the mean over the M
+// points, divide by the largest point norm.  One workgroup per cloud, three passes over it:
+//   1. the mean, summed in fp64 in one fixed order, rounded to fp32 (centroid_out);
+//   2. s = max_i |fl32(p_i - mean)|, the norm formed in fp64 (scale_out = fl32(s));
+//   3. out = fl32(fl32(p - mean) / s), the quotient formed in fp64: one rounding.
+// Passes 1 and 2 end at a barrier before pass 3 writes, so out may be pts itself.  A cloud whose s is 0 (all points
+// equal, M = 1) or not finite comes out as NaN: the maximum keeps a NaN once it has met one.
+// ------------------------------------------------------------------------------------------
+constexpr int NC_T = 512;
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+
+__global__ __launch_bounds__(NC_T) void normalize_cloud_kernel(const float* pts, float* out, int M,
+                                                               float* __restrict__ centroid_out,
+                                                               float* __restrict__ scale_out) {
+  __shared__ double s_red[NC_T / GEOA3_WAVE][3];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* P = pts + (size_t)b * 3 * M;
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int j = tid; j < M; j += NC_T) {
+    sx += (double)P[j];
+    sy += (double)P[M + j];
+    sz += (double)P[2 * M + j];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sx += __shfl_xor(sx, o, 64);
+    sy += __shfl_xor(sy, o, 64);
+    sz += __shfl_xor(sz, o, 64);
+  }
+  if (lane == 0) {
+    s_red[wave][0] = sx;
+    s_red[wave][1] = sy;
+    s_red[wave][2] = sz;
+  }
+  __syncthreads();
+  sx = sy = sz = 0.0;
+  for (int w = 0; w < NC_T / GEOA3_WAVE; ++w) {
+    sx += s_red[w][0];
+    sy += s_red[w][1];
+    sz += s_red[w][2];
+  }
+  const float mx = (float)(sx / (double)M), my = (float)(sy / (double)M), mz = (float)(sz / (double)M);
+  double best = 0.0;
+  for (int j = tid; j < M; j += NC_T) {
+    const double x = (double)(P[j] - mx), y = (double)(P[M + j] - my), z = (double)(P[2 * M + j] - mz);
+    best = nan_max(best, sqrt(x * x + y * y + z * z));
+  }
+  for (int o = 32; o > 0; o >>= 1) best = nan_max(best, __shfl_xor(best, o, 64));
+  __syncthreads();   // every thread has read pass 1's sums
+  if (lane == 0) s_red[wave][0] = best;
+  __syncthreads();
+  best = 0.0;
+  for (int w = 0; w < NC_T / GEOA3_WAVE; ++w) best = nan_max(best, s_red[w][0]);
+  const double dnan = __longlong_as_double(0x7ff8000000000000ll);
+  const double s = (best > 0.0 && best < (double)INF) ? best : dnan;
+  if (tid == 0) {
+    if (centroid_out) {
+      centroid_out[(size_t)b * 3 + 0] = mx;
+      centroid_out[(size_t)b * 3 + 1] = my;
+      centroid_out[(size_t)b * 3 + 2] = mz;
+    }
+    if (scale_out) scale_out[b] = (float)s;
+  }
+  float* O = out + (size_t)b * 3 * M;
+  for (int j = tid; j < M; j += NC_T) {
+    const float x = P[j] - mx, y = P[M + j] - my, z = P[2 * M + j] - mz;
+    O[j] = (float)((double)x / s);
+    O[M + j] = (float)((double)y / s);
+    O[2 * M + j] = (float)((double)z / s);
+  }
 }
 
 // estimate_perpendicular's tail (Lib/utility.py:146-149): clamp(v1*aux1) + clamp(v2*aux2), v1 = eigenvector of the
@@ -543,6 +708,24 @@ extern "C" int geoa3_local_frames(const float* pc, const int32_t* knn_idx, int B
   if (!pc || !knn_idx || !evals || !evecs || B <= 0 || N <= 0 || K1 < 3) return GEOA3_EINVAL;
   hipLaunchKernelGGL(local_frame_kernel, dim3((N + 255) / 256, B), dim3(256), 0, geoa3_stream(stream), pc, knn_idx, N,
                      K1, evals, evecs);
+  GEOA3_CHECK_LAUNCH();
+  return GEOA3_OK;
+}
+
+extern "C" int geoa3_estimate_normal(const float* pc, const int32_t* knn_idx, int B, int N, int K1, int orient,
+                                     float* normal_out, void* stream) {
+  if (!pc || !knn_idx || !normal_out || B <= 0 || N <= 0 || K1 < 3 || (orient != 0 && orient != 1)) return GEOA3_EINVAL;
+  hipLaunchKernelGGL(estimate_normal_kernel, dim3((N + EN_T - 1) / EN_T, B), dim3(EN_T), 0, geoa3_stream(stream), pc,
+                     knn_idx, N, K1, orient, normal_out);
+  GEOA3_CHECK_LAUNCH();
+  return GEOA3_OK;
+}
+
+extern "C" int geoa3_normalize_cloud(const float* pts, float* out, int B, int M, float* centroid_out, float* scale_out,
+                                     void* stream) {
+  if (!pts || !out || B <= 0 || M <= 0) return GEOA3_EINVAL;
+  hipLaunchKernelGGL(normalize_cloud_kernel, dim3(B), dim3(NC_T), 0, geoa3_stream(stream), pts, out, M, centroid_out,
+                     scale_out);
   GEOA3_CHECK_LAUNCH();
   return GEOA3_OK;
 }

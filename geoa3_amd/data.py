@@ -17,19 +17,55 @@ TEN_LABEL_INDEXES = [17, 9, 36, 20, 3, 16, 34, 38, 23, 15]
 TEN_LABEL_NAMES = ["airplane", "bed", "bookshelf", "bottle", "chair", "monitor", "sofa", "table", "toilet", "vase"]
 
 
+def prepare_clouds(mat, resample_num=-1, estimate_normal_knn=0, estimate_normal_orient=None, what="the data file"):
+    """The arrays of a loaded `.mat` -> (data [M,3,N'] f32, normal [M,3,N'] f32, label) CPU tensors: normals estimated
+    when the file holds none (estimate_normal_knn > 0), then all instances re-sampled to resample_num points
+    (resample_num > 0).  Both steps run on the GPU, all instances in one batched call; without either the arrays pass
+    through."""
+    from ._lib import Geoa3Error
+    data, label = torch.FloatTensor(mat["data"]), mat["label"]
+    has_normal = "normal" in mat
+    if not has_normal and estimate_normal_knn <= 0:
+        raise Geoa3Error("%s holds no `normal` array: give estimate_normal_knn > 0 (--estimate_normal_knn K) to estimate "
+                         "the normals from every point's K nearest neighbours" % what)
+    normal = torch.FloatTensor(mat["normal"]) if has_normal else None
+    if has_normal and resample_num <= 0:
+        return data, normal, label
+    if not torch.cuda.is_available():
+        raise Geoa3Error("re-sampling the input file (resample_num > 0) and estimating its normals (estimate_normal_knn "
+                         "> 0) run on the GPU, and none is present")
+    from . import utility as U
+    M, _, n = data.shape
+    first = None
+    if resample_num > 0:   # one draw per instance, in file order (Provider/modelnet10_instance250.py:110)
+        first = torch.as_tensor(np.array([np.random.randint(n) for _ in range(M)], dtype=np.int64))
+    pts = data.cuda().contiguous()
+    nrm = normal.cuda().contiguous() if has_normal else U.estimate_normal(pts, int(estimate_normal_knn),
+                                                                          estimate_normal_orient)
+    if resample_num > 0:
+        pts, nrm = U.farthest_points_normalized(pts, nrm, int(resample_num), first.cuda())
+    return pts.cpu(), nrm.cpu(), label
+
+
 class ModelNet40(torch.utils.data.Dataset):
     """Same constructor, fields (`start_index`, `data`, `normal`, `label`) and item layout as the reference class.
     item = [pcs [l,N,3], normals [l,N,3], gt_labels [l] (, target_labels [l])] with l = 9 for `All` / a class
-    name (the nine other ModelNet10 labels as targets) and l = 1 for `Untarget` / `Random`."""
+    name (the nine other ModelNet10 labels as targets) and l = 1 for `Untarget` / `Random`.
+
+    resample_num > 0 (Provider/modelnet10_instance250.py:28-36,109-126): every instance is re-sampled to resample_num
+    points by farthest-point sampling, centred and scaled to unit largest norm, all instances in one batched GPU call;
+    the first index of instance j is the j-th np.random.randint(n) draw, as the reference draws them.
+    estimate_normal_knn > 0 (extension): a file without a `normal` array gets PCA normals from that many neighbours,
+    estimated on the full cloud (estimate_normal_orient: None or "outward") before any re-sampling gathers them; a file
+    that holds `normal` keeps its own."""
 
     def __init__(self, data_mat_file="../Data/modelnet10_250instances_1024.mat", attack_label="All", resample_num=-1,
-                 is_half_forward=False):
+                 is_half_forward=False, estimate_normal_knn=0, estimate_normal_orient=None):
         if not os.path.isfile(data_mat_file):
             raise AssertionError("No exists .mat file!")
-        if resample_num > 0:
-            raise NotImplementedError("FPS re-sampling of the input file (resample_num > 0) is not on the hot path")
         mat = loadmat(data_mat_file)
-        data, normal, label = torch.FloatTensor(mat["data"]), torch.FloatTensor(mat["normal"]), mat["label"]
+        data, normal, label = prepare_clouds(mat, resample_num, estimate_normal_knn, estimate_normal_orient,
+                                             what=data_mat_file)
         self.attack_label, self.is_half_forward = attack_label, is_half_forward
         if attack_label in TEN_LABEL_NAMES:            # 25 instances of one class
             k = TEN_LABEL_NAMES.index(attack_label)

@@ -70,6 +70,83 @@ def farthest_points_sample(obj_points: Tensor, num_points: int, start: Optional[
     return pts
 
 
+def _require_gpu(*tensors: Tensor) -> None:
+    for t in tensors:
+        if not t.is_cuda:
+            raise _lib.Geoa3Error("geoa3_amd.utility has no CPU path: pass GPU tensors")
+
+
+def farthest_points_normal_sample(obj_points: Tensor, obj_normal: Tensor, num_points: int,
+                                  start: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Lib/utility.py:189-203: ([b,3,n], [b,3,n]) -> ([b,3,num_points], [b,3,num_points]), the normals taken at the
+    indices the sampler picks on the points; differentiable in both inputs like the reference's torch.gather.
+    start [b]: the first index (default: torch.randint as :194)."""
+    assert obj_points.size(1) == 3
+    assert obj_points.size(2) == obj_normal.size(2)
+    _require_gpu(obj_points, obj_normal)
+    _, idx = fps_indices(obj_points.detach(), num_points, start)
+    return _GatherPlanar.apply(obj_points, idx), _GatherPlanar.apply(obj_normal, idx)
+
+
+def normalize_cloud(points: Tensor, return_stats: bool = False):
+    """[b,3,m] -> (points - mean over the m points) / largest point norm (the tail of
+    Provider/modelnet10_instance250.py:109-126); with return_stats also (centroid [b,3], scale [b]).  A cloud whose
+    largest norm is 0 or not finite comes out NaN.  Not differentiable: the dataset's re-sampling runs without grad."""
+    _require_gpu(points)
+    b, _, m = points.shape
+    pts = points.detach().to(torch.float32).contiguous()
+    out = torch.empty_like(pts)
+    cen = torch.empty(b, 3, device=pts.device, dtype=torch.float32)
+    scale = torch.empty(b, device=pts.device, dtype=torch.float32)
+    check(_lib.load().geoa3_normalize_cloud(_p(pts), _p(out), b, m, _p(cen), _p(scale), _stream()),
+          "geoa3_normalize_cloud")
+    return (out, cen, scale) if return_stats else out
+
+
+def farthest_points_normalized(points: Tensor, normals: Tensor, num_points: int,
+                               start: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """__farthest_points_normalized of Provider/modelnet10_instance250.py:109-126 for a batch: farthest-point
+    sampling, then the selected points centred on their mean and scaled to unit largest norm; the normals are gathered
+    and left untouched.  start [b]: the first index (the reference draws np.random.randint(n) per instance, :110)."""
+    with torch.no_grad():
+        pts, nrm = farthest_points_normal_sample(points, normals, num_points, start)
+        return normalize_cloud(pts), nrm
+
+
+_ORIENT = {None: 0, "none": 0, "outward": 1}
+
+
+def estimate_normal(pc: Tensor, k: int, orient: Optional[str] = None, knn_idx: Optional[Tensor] = None) -> Tensor:
+    """Lib/utility.py:40-89: [b,3,n] -> unit normals [b,3,n], the eigenvector of the smallest eigenvalue of the
+    covariance of every point's k nearest neighbours (the point itself left out), under no_grad like the reference.
+    knn_idx int32 [b,n,k+1]: the self K-NN table when the caller already holds it.
+
+    The sign is NOT the reference's: its rule (:62-64) takes the sign of the normal's dot product with the sum of the
+    mean-centred neighbours, a sum that is zero up to rounding, so it returns noise and can zero a normal through
+    sign(0).  Here orient=None returns the eigenvector with its largest-magnitude component positive (bit for bit
+    local_frames(pc, k)[1][:, 0]); orient="outward" makes <n, p - centroid of the cloud> >= 0.  The attack loop reads
+    normals through abs(<v, n>) and (o.n) n only, so either is a complete input for it; only
+    estimate_normal_via_ori_normal, which averages normals, needs a consistent orientation.
+    A neighbourhood that holds a non-finite coordinate gives a NaN normal."""
+    if orient not in _ORIENT:
+        raise ValueError("orient must be None or 'outward', not %r" % (orient,))
+    _require_gpu(pc)
+    if k < 2:
+        raise ValueError("estimate_normal needs k >= 2 neighbours (a covariance with the factor 1/(k-1))")
+    with torch.no_grad():
+        b, _, n = pc.shape
+        pc = pc.detach().to(torch.float32).contiguous()
+        if knn_idx is None:
+            _, knn_idx = knn_planar(pc, pc, k + 1)
+        elif tuple(knn_idx.shape) != (b, n, k + 1):
+            raise ValueError("knn_idx must be [b,n,k+1] = %r, not %r" % ((b, n, k + 1), tuple(knn_idx.shape)))
+        _require_gpu(knn_idx)
+        out = torch.empty(b, 3, n, device=pc.device, dtype=torch.float32)
+        check(_lib.load().geoa3_estimate_normal(_p(pc), _p(knn_idx.contiguous(), torch.int32), b, n, k + 1,
+                                                _ORIENT[orient], _p(out), _stream()), "geoa3_estimate_normal")
+    return out
+
+
 def estimate_normal_via_ori_normal(pc_adv: Tensor, pc_ori: Tensor, normal_ori: Tensor, k: int) -> Tensor:
     """Lib/utility.py:91-108, batched per instance: [b,3,n], [b,3,N], [b,3,N] -> [b,3,n]."""
     b, _, n = pc_adv.shape

@@ -564,6 +564,21 @@ int geoa3_knn_normal(const float* knn_d, const int32_t* knn_i, const float* norm
  * largest-magnitude component positive. */
 int geoa3_local_frames(const float* pc, const int32_t* knn_idx, int B, int N, int K1, float* evals, float* evecs,
                        void* stream);
+/* estimate_normal, Lib/utility.py:40-89: normal_out [B,3,N] = the unit eigenvector of the smallest eigenvalue of the
+ * covariance geoa3_local_frames forms from knn_idx [B,N,K1] (K1 >= 3, column 0 dropped) -- the same device code, the
+ * same bits as its evecs[:,0].  orient 0: largest-magnitude component positive.  orient 1 ("outward"): the sign makes
+ * n.(p_i - c) >= 0, c = the centroid of the cloud summed in a fixed order (no atomics); a dot product of exactly 0 keeps
+ * the orient-0 sign.  The reference's own rule (:62-64, the sign of n.(sum of the mean-centred neighbours), a sum that is
+ * zero up to rounding) is NOT mirrored.  A row that lists a point with a non-finite coordinate gives a NaN normal; under
+ * orient 1 a non-finite coordinate anywhere in a cloud makes all of that cloud's normals NaN. */
+int geoa3_estimate_normal(const float* pc, const int32_t* knn_idx, int B, int N, int K1, int orient, float* normal_out,
+                          void* stream);
+/* The tail of __farthest_points_normalized, Provider/modelnet10_instance250.py:120-124 (and of
+ * Provider/gen_data_mat_sample_from10000.py:18-22): out [B,3,M] = (pts - mean over the M points) / largest point norm.
+ * out may be pts (in place).  centroid_out [B,3] / scale_out [B] (optional): the mean subtracted and the norm divided
+ * by.  One workgroup per cloud, fixed reduction order.  A cloud whose largest norm is 0 or not finite comes out NaN. */
+int geoa3_normalize_cloud(const float* pts, float* out, int B, int M, float* centroid_out, float* scale_out,
+                          void* stream);
 /* estimate_perpendicular's tail, Lib/utility.py:146-149: out [B,3,N] = clamp(v_max*aux1, +-clip) +
  * clamp(v_mid*aux2, +-clip); aux1/aux2 [B,N] = sigma * N(0,1) drawn by the caller. */
 int geoa3_perp_jitter(const float* evecs, const float* aux1, const float* aux2, int B, int N, float clip, float* out,

@@ -92,6 +92,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--corr_normal_loss_weight", type=float, default=0.0,
                    help="add w * mean_i corresponding_normal_loss(adv, normal, corr_normal_loss_knn) to the constrain loss")
     p.add_argument("--corr_normal_loss_knn", type=int, default=2)
+    p.add_argument("--resample_num", type=int, default=-1,
+                   help="> 0: re-sample every instance of the data files to this many points by farthest-point sampling, "
+                        "centred and scaled to unit radius (the reference dataset's resample_num), on the GPU")
+    p.add_argument("--estimate_normal_knn", type=int, default=0,
+                   help="> 0: a data file without a `normal` array gets PCA normals from this many neighbours")
+    p.add_argument("--estimate_normal_orient", default="none", choices=["none", "outward"],
+                   help="sign of the estimated normals: largest component positive, or pointing away from the centroid")
     p.add_argument("--out_root", default="Exps", type=str, help="root of the output tree (reference: Exps)")
     p.add_argument("--quiet", action="store_true", default=False)
     p.add_argument("--synthetic_npoint", type=int, default=0,
@@ -140,6 +147,13 @@ def saved_dir_name(cfg) -> str:
             name += "_PreJitter" + str(cfg.jitter_sigma) + "_" + str(cfg.jitter_clip)
             name += "_PreviousMethod" if cfg.is_previous_jitter_input else \
                 "_estNormalVery" + str(cfg.calculate_project_jitter_noise_iter)
+        # the input-side extensions come last, after every suffix the reference knows
+        if getattr(cfg, "resample_num", -1) > 0:
+            name += "_Resample" + str(cfg.resample_num)
+        if getattr(cfg, "estimate_normal_knn", 0) > 0:
+            name += "_EstNormal_k" + str(cfg.estimate_normal_knn)
+            if getattr(cfg, "estimate_normal_orient", "none") == "outward":
+                name += "_outward"
     else:
         assert cfg.attack is None
         name = "Evaluating_" + str(cfg.id)
@@ -275,12 +289,15 @@ def main(cfg):
             write_synthetic_mat(cfg.data_dir_file, labels, cfg.synthetic_npoint or cfg.npoint, seed=0, kind=cfg.synthetic_kind)
         if world > 1:
             dist.barrier()
-    dataset = ModelNet40(data_mat_file=cfg.data_dir_file, attack_label=cfg.attack_label, resample_num=-1)
+    orient = None if cfg.estimate_normal_orient == "none" else cfg.estimate_normal_orient
+    input_kw = dict(resample_num=cfg.resample_num, estimate_normal_knn=cfg.estimate_normal_knn,
+                    estimate_normal_orient=orient)
+    dataset = ModelNet40(data_mat_file=cfg.data_dir_file, attack_label=cfg.attack_label, **input_kw)
     loader = torch.utils.data.DataLoader(dataset, batch_size=cfg.batch_size, shuffle=False, drop_last=False,
                                          num_workers=0, pin_memory=True)
     dense_iter = None
     if cfg.is_save_normal and cfg.dense_data_dir_file is not None:   # main_attack.py:124-130
-        dense = ModelNet40(data_mat_file=cfg.dense_data_dir_file, attack_label=cfg.attack_label, resample_num=-1)
+        dense = ModelNet40(data_mat_file=cfg.dense_data_dir_file, attack_label=cfg.attack_label, **input_kw)
         dense_iter = iter(torch.utils.data.DataLoader(dense, batch_size=cfg.batch_size, shuffle=False,
                                                       drop_last=False, num_workers=0, pin_memory=True))
     elif cfg.is_save_normal:

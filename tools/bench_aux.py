@@ -38,6 +38,20 @@ def main():
     print("local_frames B=250 N=1024 k=16 : %.3f ms" % timeit(lambda: U.local_frames(pc1, 16, idx)))
     print("estimate_perpendicular k=16    : %.3f ms" % timeit(lambda: U.estimate_perpendicular(pc1, 16)))
     print("smoothness k=16 k2=16          : %.3f ms" % timeit(lambda: U.smoothness(pc1, 16, 16)))
+    # the input side: PCA normals and the re-sampling's normalisation, at the victim's size and at the dense file's
+    print("estimate_normal k=16 N=1024 (table given)   : %.3f ms" % timeit(lambda: U.estimate_normal(pc1, 16, None, idx)))
+    print("estimate_normal k=16 N=1024 outward (given) : %.3f ms" % timeit(
+        lambda: U.estimate_normal(pc1, 16, "outward", idx)))
+    print("estimate_normal k=16 N=1024 with its search : %.3f ms" % timeit(lambda: U.estimate_normal(pc1, 16)))
+    print("normalize_cloud B=250 M=1024                : %.3f ms" % timeit(lambda: U.normalize_cloud(pc1)))
+    pc10 = torch.as_tensor(synthetic_clouds(B, 10000, 2)[0]).to(dev)
+    _, idx10 = ops.knn_planar(pc10, pc10, 17)
+    print("self K-NN K=17 N=10000 (all pairs)          : %.3f ms" % timeit(lambda: ops.knn_planar(pc10, pc10, 17), n=3, warm=1))
+    print("estimate_normal k=16 N=10000 (table given)  : %.3f ms" % timeit(lambda: U.estimate_normal(pc10, 16, None, idx10)))
+    print("estimate_normal k=16 N=10000 outward (given): %.3f ms" % timeit(
+        lambda: U.estimate_normal(pc10, 16, "outward", idx10)))
+    print("normalize_cloud B=250 M=10000               : %.3f ms" % timeit(lambda: U.normalize_cloud(pc10)))
+    del pc10, idx10
     adv = pc4[:, :, :1024].contiguous()
     print("estimate_normal_via_ori k=3 1024 vs 4096: %.3f ms" % timeit(
         lambda: U.estimate_normal_via_ori_normal(adv, pc4, nrm4, 3)))
