@@ -355,7 +355,9 @@ int geoa3_attack_project(int mode, const float* ori, const float* normal_ori, co
                          float* x, int B, int N, float cc_linf, void* stream);
 
 /* End of a binary step: the scale_const / bound update of geoA3_attack.py:374-384, bug-compatible
- * (uses *last_label for every instance).  Also re-arms the per-binary-step state. */
+ * (uses *last_label for every instance).  It touches scale_const and the two bounds only: the per-binary-step state
+ * (iter_best_*, prev_constrain) is re-armed by geoa3_attack_begin_search_step, as the reference resets it at the top of
+ * its loop (:231-233). */
 int geoa3_attack_binary_update(const geoa3_attack_state* st, void* stream);
 
 /* Start of a binary step: offset <- init_offset, adam state <- 0, x = ori + offset, per-step state reset. */
