@@ -33,6 +33,56 @@ def _cfg(cfg, name, default):
     return getattr(cfg, name, default)
 
 
+def knn_table_plan(use_curv, k, w_disp, k_disp, w_rep, k_rep, w_cn, k_cn, w_knn, ks, knn_share_table=True,
+                   reg_share_table=True):
+    """Which neighbour table each active neighbour term reads and how many columns it has: ({term: (table, columns)},
+    geoa3_knn_self launches per iteration).  Terms: "knn" (kNN smoothing), "disp", "rep", "cn".  Tables: "curv" the curvature
+    term's (of this iteration's iterate; for "disp" the clean cloud's, built with it once per batch), whose first columns
+    hold the nearer neighbours of any narrower term; "own" the smoothing term's own search; "reg" the ONE search the
+    repulsion and normal terms share; "clean" the displacement term's own table of the clean cloud, once per batch.
+    The *_share_table switches (tests) refuse the curvature term's table."""
+    curv, plan = ("curv", k + 1), {}
+    if w_knn != 0:
+        plan["knn"] = curv if use_curv and ks <= k and knn_share_table else ("own", ks + 1)
+    if w_disp != 0:
+        plan["disp"] = curv if use_curv and k_disp <= k else ("clean", k_disp + 1)
+    if w_rep != 0 or w_cn != 0:
+        kmax = max(k_rep if w_rep != 0 else 1, k_cn if w_cn != 0 else 1)
+        reg = curv if use_curv and kmax <= k and reg_share_table else ("reg", kmax + 1)
+        plan.update({term: reg for term, w in (("rep", w_rep), ("cn", w_cn)) if w != 0})
+    return plan, int(use_curv) + len({table for table, _ in plan.values() if table in ("own", "reg")})
+
+
+class _SelfKnnTable:
+    """A self-K-NN table of the iterate, searched once per iteration: double-buffered, last iteration's table being the
+    prior of this one's search.  The buffers live in the runner's t under prefix + "knn" / "knn_d" / "scratch"."""
+
+    def __init__(self, t: dict, prefix: str, b: int, ne: int, cols: int, device, method: int = 0):
+        self.b, self.ne, self.cols, self.method = b, ne, cols, method   # method: geoa3_knn_self's, 0 = by (K, N)
+        self.idx = t[prefix + "knn"] = [torch.zeros(b, ne, cols, device=device, dtype=torch.int32) for _ in range(2)]
+        self.d = t[prefix + "knn_d"] = torch.zeros(b, ne, cols, device=device, dtype=torch.float32)
+        # the searches of an iteration follow each other on one stream: the curvature term's scratch, when there is one,
+        # serves the other tables too
+        self.scratch = t[(prefix or "knn_") + "scratch"] = (t["knn_scratch"] if "knn_scratch" in t
+                                                            else ops.knn_self_scratch(b, ne, device))
+        self.knn_self = _lib.load().geoa3_knn_self      # looked up, like the buffers' addresses, once
+        self.ptrs = [x.data_ptr() for x in (*self.idx, self.d, self.scratch)]
+
+    def reset(self, clean_idx: Optional[Tensor]):
+        """A new batch: the clean cloud's table [b,ne,cols] is the first prior (None: the first search has none)."""
+        self.cur, self.seeded = 0, clean_idx is not None
+        if self.seeded:
+            self.idx[0].copy_(clean_idx)
+
+    def search(self, xe: Tensor, stream: int):
+        """-> (dists [b,ne,cols], idx, cols) of xe, enqueued on stream"""
+        prior, out = self.ptrs[self.cur] if self.seeded else None, self.ptrs[1 - self.cur]
+        check(self.knn_self(xe.data_ptr(), self.b, self.ne, self.cols, prior, self.ptrs[2], out, self.ptrs[3],
+                            self.method, stream), "knn_self")
+        self.seeded, self.cur = True, 1 - self.cur
+        return self.d, self.idx[self.cur], self.cols
+
+
 class AttackRunner:
     """Owns the device state of one batch of b attacks in flight and enqueues the loop."""
 
@@ -54,11 +104,10 @@ class AttackRunner:
             raise AssertionError("Not support such optimizer.")
         self.net, self.cfg, self.b, self.n, self.dev = net, cfg, b, n, device
         self.lib = _lib.load()
-        # Native victim: the PointNet whose forward / input-gradient live in the HIP library.  Any other eval-mode
-        # nn.Module (PointNet++ SSG on the HIP set-abstraction operators, geoa3_amd/pointnet2.py) is driven through
-        # torch autograd: logits = net(x); logits.backward(dlogits) -- still no host synchronisation.
-        # ... and the PointNet++ SSG classifier of geoa3_amd/pointnet2.py (eval mode, xyz only) is native too:
-        # geoa3_pn2ssg_forward / _backward (csrc/pointnet2_net.hip)
+        # Native victims, whose forward / input-gradient live in the HIP library: the PointNet, and the PointNet++ SSG
+        # classifier of geoa3_amd/pointnet2.py in eval mode on xyz only (geoa3_pn2ssg_forward / _backward,
+        # csrc/pointnet2_net.hip).  Any other eval-mode nn.Module is driven through torch autograd:
+        # logits = net(x); logits.backward(dlogits) -- still no host synchronisation.
         from .pointnet2 import PointNet2ClassificationSSG
         self.ssg = (isinstance(net, PointNet2ClassificationSSG) and not net.training and not net.use_normal and
                     min(n, int(_cfg(cfg, "npoint", n))) >= PointNet2ClassificationSSG.MIN_POINTS)
@@ -78,6 +127,8 @@ class AttackRunner:
         self.use_curv = cfg.curv_loss_weight != 0
         self.dis_type = {"CD": 1, "L2": 2, "None": 0}[cfg.dis_loss_type]
         self.need_nn = self.dis_type == 1 or cfg.hd_loss_weight != 0 or self.use_curv
+        self.geo_runs = self.need_nn or self.dis_type == 2     # the geometric objective runs at all: L2 needs no 1-NN
+        self.both = self.dis_type == 1 and not cfg.is_cd_single_side      # two-sided Chamfer: the clean cloud's 1-NN too
         self.iters = int(cfg.iter_max_steps)
         # the objective's gradient summed in a fixed order (geoa3_geo_args.deterministic): iterates are reproducible bit
         # for bit and shard rows equal the full batch's; cfg.deterministic / GEOA3_DETERMINISTIC=0 select the atomics
@@ -169,25 +220,10 @@ class AttackRunner:
         self.geo_scratch = (ops.geo_scratch(b, ne, device, self.k)
                             if (((1024 < ne or self.k > 32) and ne <= 4096 and self.use_curv)
                                 or ops.GEO_WIDE_MIN_N <= ne <= 8192) else None)
-        if self.use_curv:
-            t["knn"] = [torch.zeros(b, ne, self.k + 1, **i32) for _ in range(2)]
-            t["knn_d"] = z(b, ne, self.k + 1)
-            self.knn_method = int(_cfg(cfg, "knn_method", 0))   # geoa3_knn_self: 0 = by (K, N), 1 = slab, 2 = cell grid
-            t["knn_scratch"] = ops.knn_self_scratch(b, ne, device)
-        if self.w_knn != 0:
-            self.ks = int(_cfg(cfg, "knn_smoothing_k", 5))
-            self.knn_coef = float(_cfg(cfg, "knn_threshold_coef", 1.10))
-            if not 1 <= self.ks < min(ne, 64):
-                raise ValueError("knn_smoothing_k must be in 1..%d" % (min(ne, 64) - 1))
-            # the curvature term's table of this iteration holds the ks + 1 nearest in its first columns
-            # (cfg.knn_smoothing_share_table = False: tests, a search of its own)
-            self.knn_share = self.use_curv and self.ks <= self.k and bool(_cfg(cfg, "knn_smoothing_share_table", True))
-            t["ks_loss"], t["ks_grad"] = z(b), z(b, 3, ne)
-            self.ks_ws = ops.reg_workspace(b, ne, self.ks, device)
-            if not self.knn_share:
-                t["ks_knn"] = [torch.zeros(b, ne, self.ks + 1, **i32) for _ in range(2)]
-                t["ks_knn_d"] = z(b, ne, self.ks + 1)
-                t["ks_scratch"] = t["knn_scratch"] if self.use_curv else ops.knn_self_scratch(b, ne, device)
+        self.ks = int(_cfg(cfg, "knn_smoothing_k", 5))
+        self.knn_coef = float(_cfg(cfg, "knn_threshold_coef", 1.10))
+        if self.w_knn != 0 and not 1 <= self.ks < min(ne, 64):
+            raise ValueError("knn_smoothing_k must be in 1..%d" % (min(ne, 64) - 1))
         # --displacement_loss_weight / --repulsion_loss_weight / --corr_normal_loss_weight (extensions): the per-point
         # regularisers of Lib/loss_utils.py:99-123 on the cloud the objective sees, each through its mean over the points
         # (as curvature_loss reduces its own, :95).  Per row: a sharded batch needs nothing.
@@ -208,33 +244,40 @@ class AttackRunner:
             raise ValueError("displacement_loss_weight / corr_normal_loss_weight != 0 cannot be combined with the dense "
                              "sub-sample path (is_subsample_opt with n > npoint): point i of the sample is not point i of "
                              "the clean cloud")
-        if self.w_disp != 0 or self.w_rep != 0 or self.w_cn != 0:
-            self.reg_ws = ops.reg_workspace(b, ne, max(self.k_disp if self.w_disp != 0 else 1,
-                                                       self.k_rep if self.w_rep != 0 else 1,
-                                                       self.k_cn if self.w_cn != 0 else 1), device)
+        # The neighbour tables (knn_table_plan): the curvature term's table of this iteration holds the nearest of any
+        # narrower term in its first columns; a term it does not serve searches for itself, repulsion and normal with ONE
+        # search for both.  The displacement term reads the clean cloud's table, built once per batch (setup()).
+        plan, self.knn_searches_per_iteration = knn_table_plan(
+            self.use_curv, self.k, self.w_disp, self.k_disp, self.w_rep, self.k_rep, self.w_cn, self.k_cn, self.w_knn,
+            self.ks, bool(_cfg(cfg, "knn_smoothing_share_table", True)), bool(_cfg(cfg, "reg_share_table", True)))
+        self.ks_table = self.reg_table = None
+        self.curv_table = (_SelfKnnTable(t, "", b, ne, self.k + 1, device, int(_cfg(cfg, "knn_method", 0)))
+                           if self.use_curv else None)
+        if self.w_knn != 0:
+            self.knn_share = plan["knn"][0] == "curv"
+            t["ks_loss"], t["ks_grad"] = z(b), z(b, 3, ne)
+            self.ks_ws = ops.reg_workspace(b, ne, self.ks, device)
+            if not self.knn_share:
+                self.ks_table = _SelfKnnTable(t, "ks_", b, ne, plan["knn"][1], device)
+        # the per-point terms that are on, in their fold order
+        self.point_terms = [(name, w, k) for name, w, k in (("disp", self.w_disp, self.k_disp), ("rep", self.w_rep, self.k_rep),
+                                                            ("cn", self.w_cn, self.k_cn)) if w != 0]
+        for name, _, _ in self.point_terms:
+            t[name + "_out"], t[name + "_grad"], t[name + "_loss"] = z(b, ne), z(b, 3, ne), z(b)
+        if self.point_terms:
+            self.reg_ws = ops.reg_workspace(b, ne, max(k for _, _, k in self.point_terms), device)
         if self.w_disp != 0:
-            # the clean cloud's table, once per batch (setup()); the curvature term's own when it is wide enough
-            self.disp_share = self.use_curv and self.k_disp <= self.k
-            t["disp_out"], t["disp_grad"], t["disp_loss"] = z(b, ne), z(b, 3, ne), z(b)
+            self.disp_share = plan["disp"][0] == "curv"
             if not self.disp_share:
                 t["disp_knn_d"], t["disp_knn"] = z(b, n, self.k_disp + 1), torch.zeros(b, n, self.k_disp + 1, **i32)
         if self.w_rep != 0 or self.w_cn != 0:
-            # the iterate's table: the curvature term's of this iteration holds the k + 1 nearest in its first columns
-            # (cfg.reg_share_table = False: tests); otherwise ONE search of their own for both terms, double-buffered with
-            # last iteration's table as prior
-            kmax = max(self.k_rep if self.w_rep != 0 else 1, self.k_cn if self.w_cn != 0 else 1)
-            self.reg_share = self.use_curv and kmax <= self.k and bool(_cfg(cfg, "reg_share_table", True))
-            self.reg_K = (self.k if self.reg_share else kmax) + 1
+            table, self.reg_K = plan.get("rep") or plan["cn"]
+            self.reg_share = table == "curv"
             if not self.reg_share:
-                t["reg_knn"] = [torch.zeros(b, ne, self.reg_K, **i32) for _ in range(2)]
-                t["reg_knn_d"] = z(b, ne, self.reg_K)
-                t["reg_scratch"] = t["knn_scratch"] if self.use_curv else ops.knn_self_scratch(b, ne, device)
-        if self.w_rep != 0:
-            t["rep_out"], t["rep_grad"], t["rep_loss"] = z(b, ne), z(b, 3, ne), z(b)
+                self.reg_table = _SelfKnnTable(t, "reg_", b, ne, self.reg_K, device)
         if self.w_cn != 0:
             # corresponding_normal_loss = geoa3_kappa with the point's own normal (a table of exactly k + 1 columns); its
             # gradient = geoa3_corr_normal_loss_grad, pair terms in double
-            t["cn_out"], t["cn_grad"], t["cn_loss"] = z(b, ne), z(b, 3, ne), z(b)
             t["cn_knn"] = torch.zeros(b, ne, self.k_cn + 1, **i32)   # the table's first k + 1 columns, inside the cloud
         if self.native:
             bw = b * self.eval_num if self.sub else b
@@ -284,26 +327,19 @@ class AttackRunner:
         if self.use_curv:  # _get_kappa_ori once per batch (geoA3_attack.py:216-217)
             knn_ori_d, knn_ori = ops.knn_planar(self.ori, self.ori, self.k + 1)
             self.kappa_ori = ops.kappa(self.ori, self.nrm, knn_ori)
-            self.knn_cur = 0
-            self.knn_seeded = not self.sub
-            if self.knn_seeded:
-                t["knn"][0].copy_(knn_ori)
-        if self.w_knn != 0 and not self.knn_share:   # the prior of the term's own search: the clean cloud's neighbours
-            self.ks_cur = 0
-            self.ks_seeded = not self.sub
-            if self.ks_seeded:
-                t["ks_knn"][0].copy_(ops.knn_planar(self.ori, self.ori, self.ks + 1)[1])
+            self.curv_table.reset(None if self.sub else knn_ori)
+        # the first prior of a term's own search: the clean cloud's neighbours (none for a sample: other points)
+        own_prior = lambda tb: None if self.sub else ops.knn_planar(self.ori, self.ori, tb.cols)[1]
+        if self.ks_table is not None:
+            self.ks_table.reset(own_prior(self.ks_table))
         if self.w_disp != 0:   # displacement_loss reads the CLEAN cloud's neighbours (Lib/loss_utils.py:101): once per batch
             if self.disp_share:
                 self.disp_table = (knn_ori_d, knn_ori, self.k + 1)
             else:
                 ops.knn_planar(self.ori, self.ori, self.k_disp + 1, out=(t["disp_knn_d"], t["disp_knn"]))
                 self.disp_table = (t["disp_knn_d"], t["disp_knn"], self.k_disp + 1)
-        if (self.w_rep != 0 or self.w_cn != 0) and not self.reg_share:   # the prior of the two terms' own search
-            self.reg_cur = 0
-            self.reg_seeded = not self.sub
-            if self.reg_seeded:
-                t["reg_knn"][0].copy_(ops.knn_planar(self.ori, self.ori, self.reg_K)[1])
+        if self.reg_table is not None:
+            self.reg_table.reset(own_prior(self.reg_table))
         cls_type = {"None": 0, "CE": 1, "Margin": 2}[cfg.cls_loss_type]
         self.state = AttackState(
             B=self.b, N=self.n, classes=self.classes, targeted=int(self.targeted), cls_loss_type=cls_type,
@@ -346,11 +382,6 @@ class AttackRunner:
                 st.flags &= ~4
         self._ws_fwd_shape = shape
 
-    def _native_backward(self, pts: Tensor, dlogits: Tensor, dx: Tensor, s: int):
-        fn = self.lib.geoa3_pn2ssg_backward if self.ssg else self.lib.geoa3_pointnet_backward
-        check(fn(C.byref(self.packed.struct), pts.data_ptr(), dlogits.data_ptr(), pts.shape[0], pts.shape[2],
-                 dx.data_ptr(), self.ws.data_ptr(), s), "victim backward")
-
     def _victim_labels_logits(self, pts: Tensor, out: Tensor):
         """logits of the victim on pts [B',3,m] (no gradient kept) -> out [B',classes]."""
         if self.native:
@@ -370,252 +401,275 @@ class AttackRunner:
         iterate t["x"]: fills logits / cls_loss / loss_n / the distance losses and returns the two gradient parts
         (g_cls [b,3,n] already scaled by 1/b, g_geo [b,3,n] = d constrain / dx un-scaled; either may be None), or None
         when the step is complete (--is_partial_var keeps its own optimiser)."""
-        from . import utility as U
-        cfg, t, lib = self.cfg, self.t, self.lib
-        s = torch.cuda.current_stream().cuda_stream
-        st = C.byref(self.state)
-        x = t["x"]                      # the full iterate pc_ori + offset, [b,3,n]
-        if self.partial and step % 50 == 0:   # geoA3_attack.py:240-262
-            hook = self.hooks.get("partial_points")
-            p0 = int(hook(search_step, step)) if hook else int(np.random.randint(self.n))
-            _, nbr = ops.knn_planar(self.ori[:, :, p0:p0 + 1].contiguous(), self.ori, self.kr + 1)
-            t["pidx"].copy_(nbr[:, 0, 1:])
-            hook = self.hooks.get("partial_inits")
-            t["part"].copy_(hook(search_step, step) if hook else torch.randn(self.b, 3, self.kr, device=self.dev) * 1e-3)
-            t["pm"].zero_()
-            t["pv"].zero_()
-            t["periodical"].copy_(x)    # the iterate of the last forward (its optimiser step is dropped, as :259-262)
-            check(lib.geoa3_attack_partial_step(st, None, None, t["pidx"].data_ptr(), self.kr,
-                                                t["periodical"].data_ptr(), t["part"].data_ptr(), None, None,
-                                                x.data_ptr(), -1, 0.0, 1.0, 0.0, 0, s), "attack_partial_step")
-            self.part_t = 0
-        xe, ne = x, self.ne             # what the objective is evaluated on, [b,3,ne]
-        vote_logits = None
-        if self.sub:
-            # geoA3_attack.py:283-284: the objective's sample; :289-295: eval_num resamplings per instance for the
-            # success vote.  The reference draws the start indices with torch.randint on its device.
-            hook = self.hooks.get("sub_starts")
-            start = hook(search_step, step) if hook else torch.randint(self.n, (self.b,), device=self.dev)
-            start = start.to(self.dev, torch.int32).contiguous()
-            check(lib.geoa3_fps_sample(x.data_ptr(), self.b, self.n, ne, start.data_ptr(), t["sub_idx"].data_ptr(),
-                                       t["x_cur"].data_ptr(), s), "fps_sample")
-            xe = t["x_cur"]
-            E = self.eval_num
-            hook = self.hooks.get("vote_starts")
-            vstart = hook(search_step, step) if hook else torch.randint(self.n, (self.b, E), device=self.dev)
-            vstart = vstart.to(self.dev, torch.int32).reshape(-1).contiguous()
-            xrep = x if E == 1 else x.unsqueeze(1).expand(self.b, E, 3, self.n).reshape(self.b * E, 3, self.n)
-            check(lib.geoa3_fps_sample(xrep.data_ptr(), self.b * E, self.n, ne, vstart.data_ptr(),
-                                       t["vote_idx"].data_ptr(), t["vote_pts"].data_ptr(), s), "fps_sample")
-            self._victim_labels_logits(t["vote_pts"], t["vote_logits"])
-            vote_logits = t["vote_logits"]
-        if self.jitter:
-            if not self.sub:   # the success check sees the iterate WITHOUT the jitter (geoA3_attack.py:297 vs :317)
-                self._victim_labels_logits(x, t["check_logits"])
-                vote_logits = t["check_logits"]
-            if step % int(cfg.calculate_project_jitter_noise_iter) == 0:
-                hook = self.hooks.get("jitter_noise")
-                if hook:
-                    t["noise"].copy_(hook(search_step, step, xe))
-                else:
-                    aux = self.hooks["jitter_aux"](search_step, step) if "jitter_aux" in self.hooks else None
-                    t["noise"].copy_(U.estimate_perpendicular(xe, int(cfg.jitter_k), float(cfg.jitter_sigma),
-                                                              float(cfg.jitter_clip), aux=aux))
-            torch.add(xe, t["noise"], out=t["x_eval"])
-            xe = t["x_eval"]
-        logits_ag = x_leaf = None
         main = torch.cuda.current_stream()
-        sg, geo_ctx = s, None
-        if self.geo_stream is not None:     # xe is final on the main stream: the geometry may start
-            self.ev_x.record(main)
-            self.geo_stream.wait_event(self.ev_x)
-            sg = self.geo_stream.cuda_stream
+        s = main.cuda_stream
+        if self.partial and step % 50 == 0:
+            self._partial_redraw(step, search_step, s)
+        xe, vote_logits = self.t["x"], None     # what the objective is evaluated on [b,3,ne]; what the success check sees
+        if self.sub:
+            xe, vote_logits = self._sample_and_votes(step, search_step, s)
+        if self.jitter:
+            xe, vote_logits = self._jitter(step, search_step, xe, vote_logits)
+        late = self.late_join and self.geo_stream is not None
+        sg = self._fork_geometry(main, s)
+        autograd = self._victim_forward(xe, s)
+        constrain, geo_on = self._geometry(xe, sg, main, late)
+        self._head(late, vote_logits, constrain, step, search_step, s)
+        g_cls = self._victim_backward(xe, autograd, s) if self.cfg.cls_loss_type != "None" else None
+        if late:
+            self._head_finish(main, constrain, step, search_step, s)
+        if self.w_uni != 0:
+            g_cls = self._uniform_grad(g_cls, s)
+        g_geo = self.t["g_geo"] if geo_on else None
+        if self.sub:
+            g_cls, g_geo = self._scatter_to_full_cloud(g_cls, g_geo, s)
+        if self.partial:
+            return self._partial_update(step, g_cls, g_geo, s)
+        return g_cls, g_geo
+
+    # ---- the stages of objective(), in its order
+    def _partial_redraw(self, step: int, search_step: int, s: int):
+        """--is_partial_var, every 50 steps (geoA3_attack.py:240-262): new neighbourhood, new offset, fresh optimiser."""
+        t, x = self.t, self.t["x"]
+        hook = self.hooks.get("partial_points")
+        p0 = int(hook(search_step, step)) if hook else int(np.random.randint(self.n))
+        _, nbr = ops.knn_planar(self.ori[:, :, p0:p0 + 1].contiguous(), self.ori, self.kr + 1)
+        t["pidx"].copy_(nbr[:, 0, 1:])
+        hook = self.hooks.get("partial_inits")
+        t["part"].copy_(hook(search_step, step) if hook else torch.randn(self.b, 3, self.kr, device=self.dev) * 1e-3)
+        t["pm"].zero_()
+        t["pv"].zero_()
+        t["periodical"].copy_(x)    # the iterate of the last forward (its optimiser step is dropped, as :259-262)
+        check(self.lib.geoa3_attack_partial_step(C.byref(self.state), None, None, t["pidx"].data_ptr(), self.kr,
+                                                 t["periodical"].data_ptr(), t["part"].data_ptr(), None, None,
+                                                 x.data_ptr(), -1, 0.0, 1.0, 0.0, 0, s), "attack_partial_step")
+        self.part_t = 0
+
+    def _sample_and_votes(self, step: int, search_step: int, s: int):
+        """geoA3_attack.py:283-284: the objective's sample; :289-295: eval_num resamplings per instance for the
+        success vote.  The reference draws the start indices with torch.randint on its device.  -> (xe, vote logits)"""
+        t, lib, x, ne, E = self.t, self.lib, self.t["x"], self.ne, self.eval_num
+        hook = self.hooks.get("sub_starts")
+        start = hook(search_step, step) if hook else torch.randint(self.n, (self.b,), device=self.dev)
+        start = start.to(self.dev, torch.int32).contiguous()
+        check(lib.geoa3_fps_sample(x.data_ptr(), self.b, self.n, ne, start.data_ptr(), t["sub_idx"].data_ptr(),
+                                   t["x_cur"].data_ptr(), s), "fps_sample")
+        hook = self.hooks.get("vote_starts")
+        vstart = hook(search_step, step) if hook else torch.randint(self.n, (self.b, E), device=self.dev)
+        vstart = vstart.to(self.dev, torch.int32).reshape(-1).contiguous()
+        xrep = x if E == 1 else x.unsqueeze(1).expand(self.b, E, 3, self.n).reshape(self.b * E, 3, self.n)
+        check(lib.geoa3_fps_sample(xrep.data_ptr(), self.b * E, self.n, ne, vstart.data_ptr(),
+                                   t["vote_idx"].data_ptr(), t["vote_pts"].data_ptr(), s), "fps_sample")
+        self._victim_labels_logits(t["vote_pts"], t["vote_logits"])
+        return t["x_cur"], t["vote_logits"]
+
+    def _jitter(self, step: int, search_step: int, xe: Tensor, vote_logits: Optional[Tensor]):
+        """--is_pre_jitter_input (geoA3_attack.py:312-317) -> (xe + tangent-plane noise, vote logits)"""
+        from . import utility as U
+        cfg, t = self.cfg, self.t
+        if not self.sub:   # the success check sees the iterate WITHOUT the jitter (geoA3_attack.py:297 vs :317)
+            self._victim_labels_logits(xe, t["check_logits"])
+            vote_logits = t["check_logits"]
+        if step % int(cfg.calculate_project_jitter_noise_iter) == 0:
+            hook = self.hooks.get("jitter_noise")
+            if hook:
+                t["noise"].copy_(hook(search_step, step, xe))
+            else:
+                aux = self.hooks["jitter_aux"](search_step, step) if "jitter_aux" in self.hooks else None
+                t["noise"].copy_(U.estimate_perpendicular(xe, int(cfg.jitter_k), float(cfg.jitter_sigma),
+                                                          float(cfg.jitter_clip), aux=aux))
+        torch.add(xe, t["noise"], out=t["x_eval"])
+        return t["x_eval"], vote_logits
+
+    def _fork_geometry(self, main, s: int) -> int:
+        """xe is final on the main stream: the geometry may start beside the victim's forward.  -> its stream"""
+        if self.geo_stream is None:
+            return s
+        self.ev_x.record(main)
+        self.geo_stream.wait_event(self.ev_x)
+        return self.geo_stream.cuda_stream
+
+    def _victim_forward(self, xe: Tensor, s: int):
+        """logits of xe -> t["logits"]; -> (logits, leaf) of the autograd graph of a victim that is not native"""
+        t = self.t
         if self.native:
             self._native_forward(xe, t["logits"], s)
-        else:
-            x_leaf = xe.detach().clone().requires_grad_()
-            with torch.enable_grad():
-                logits_ag = self.net(x_leaf)
-            if logits_ag.shape != t["logits"].shape:
-                raise _lib.Geoa3Error("the victim returned logits of shape %s, expected %s (set cfg.classes)"
-                                      % (tuple(logits_ag.shape), tuple(t["logits"].shape)))
-            t["logits"].copy_(logits_ag.detach())
+            return None
+        x_leaf = xe.detach().clone().requires_grad_()
+        with torch.enable_grad():
+            logits_ag = self.net(x_leaf)
+        if logits_ag.shape != t["logits"].shape:
+            raise _lib.Geoa3Error("the victim returned logits of shape %s, expected %s (set cfg.classes)"
+                                  % (tuple(logits_ag.shape), tuple(t["logits"].shape)))
+        t["logits"].copy_(logits_ag.detach())
+        return logits_ag, x_leaf
+
+    def _geometry(self, xe: Tensor, sg: int, main, late: bool):
+        """The constraint terms on the geometry stream, each folded into constrain / g_geo (_fold), in a FIXED order:
+        objective, kNN smoothing, displacement, repulsion, normal, uniform.  -> (constrain or None, g_geo was written)"""
         with (torch.cuda.stream(self.geo_stream) if self.geo_stream is not None else contextlib.nullcontext()):
-            constrain = None
-            if self.need_nn:
-                both = self.dis_type == 1 and not cfg.is_cd_single_side
-                if self.grid_nn1:   # seeded with the tables of the previous iteration (in place)
-                    pa = t["i_ao"].data_ptr() if self.nn1_seeded else None
-                    pr = t["i_oa"].data_ptr() if self.nn1_seeded and both else None
-                    out = (t["d_ao"].data_ptr(), t["i_ao"].data_ptr(), t["d_oa"].data_ptr() if both else None,
-                           t["i_oa"].data_ptr() if both else None)
-                    if self.nn1_policy is None:
-                        check(lib.geoa3_grid_nn1_pair(xe.data_ptr(), self.ori.data_ptr(), self.b, ne, self.n, pa, pr, *out,
-                                                      sg), "grid_nn1_pair")
-                    else:
-                        check(lib.geoa3_debug_grid_nn1_pair(xe.data_ptr(), self.ori.data_ptr(), self.b, ne, self.n, pa, pr,
-                                                            *out, *self.nn1_policy, sg), "grid_nn1_pair")
-                    self.nn1_seeded = not self.sub
-                else:
-                    check(lib.geoa3_nn1_pair(xe.data_ptr(), self.ori.data_ptr(), self.b, ne, self.n,
-                                             t["d_ao"].data_ptr(), t["i_ao"].data_ptr(),
-                                             t["d_oa"].data_ptr() if both else None,
-                                             t["i_oa"].data_ptr() if both else None, sg), "nn1_pair")
-            knn_adv = None
-            if self.use_curv:
-                prior, out = t["knn"][self.knn_cur], t["knn"][1 - self.knn_cur]
-                check(lib.geoa3_knn_self(xe.data_ptr(), self.b, ne, self.k + 1,
-                                         prior.data_ptr() if self.knn_seeded else None, t["knn_d"].data_ptr(),
-                                         out.data_ptr(), t["knn_scratch"].data_ptr(),
-                                         self.knn_method, sg),
-                      "knn_self")
-                self.knn_seeded = True
-                self.knn_cur = 1 - self.knn_cur
-                knn_adv = out
-            if self.dis_type != 0 or cfg.hd_loss_weight != 0 or self.use_curv:
-                ops.geo_loss_grad(xe, self.ori, normal_ori=self.nrm if self.use_curv else None,
-                                  kappa_ori=self.kappa_ori, d_ao=t["d_ao"] if self.need_nn else None,
-                                  i_ao=t["i_ao"] if self.need_nn else None,
-                                  d_oa=t["d_oa"] if self.dis_type == 1 and not cfg.is_cd_single_side else None,
-                                  i_oa=t["i_oa"] if self.dis_type == 1 and not cfg.is_cd_single_side else None,
-                                  knn_adv=knn_adv, k=self.k if self.use_curv else 0, dis_type=self.dis_type,
-                                  single_side=bool(cfg.is_cd_single_side), w_dis=float(cfg.dis_loss_weight),
-                                  w_hd=float(cfg.hd_loss_weight), w_curv=float(cfg.curv_loss_weight), out=self.geo_out,
-                                  deterministic=self.deterministic, scratch=self.geo_scratch)
-                constrain = self.geo_out["constrain"]
-            geo_on = constrain is not None
+            self._constrain, self._geo_on = None, False
+            curv = self._distance_curvature(xe, sg) if self.geo_runs else None    # the curvature term's table, if any
             if self.w_knn != 0:
-                # S_b = kNN_smoothing_loss(xe)[b] and dS_b/dx on the geometry stream, then constrain_b (+)= w S_b (before the
-                # head reads it) and g_geo (+)= w dS_b/dx.  g_geo stays UN-scaled: attack_update_kernel multiplies all of it
-                # by scale_const[b] * inv_global_batch (= c_b / b, the gradient of mean_b(c_b constrain_b)) when it forms
-                # g = g_cls + (c_b / b) g_geo, so the term gets the factor of the other constraint terms there, once.
-                if self.knn_share:
-                    table, ld = (t["knn_d"], knn_adv), self.k + 1
-                else:
-                    prior, out = t["ks_knn"][self.ks_cur], t["ks_knn"][1 - self.ks_cur]
-                    check(lib.geoa3_knn_self(xe.data_ptr(), self.b, ne, self.ks + 1,
-                                             prior.data_ptr() if self.ks_seeded else None, t["ks_knn_d"].data_ptr(),
-                                             out.data_ptr(), t["ks_scratch"].data_ptr(), 0, sg), "knn_self")
-                    self.ks_seeded = True
-                    self.ks_cur = 1 - self.ks_cur
-                    table, ld = (t["ks_knn_d"], out), self.ks + 1
-                tb = (table[0].data_ptr(), table[1].data_ptr(), ld)
-                check(lib.geoa3_knn_smoothing_loss(xe.data_ptr(), self.b, ne, self.ks, self.knn_coef, *tb,
-                                                   t["ks_loss"].data_ptr(), None, self.ks_ws.data_ptr(), sg),
-                      "knn_smoothing_loss")
-                check(lib.geoa3_knn_smoothing_loss_grad(xe.data_ptr(), self.b, ne, self.ks, self.knn_coef, *tb, None,
-                                                        t["ks_grad"].data_ptr(), self.ks_ws.data_ptr(), sg),
-                      "knn_smoothing_loss_grad")
-                constrain = self.geo_out["constrain"]
-                ops.reg_fold(t["ks_loss"], t["ks_grad"], self.w_knn, self.b, ne, constrain=constrain, constrain_add=geo_on,
-                             g=t["g_geo"], g_add=geo_on, stream=sg)
-                geo_on = True
-            # the per-point regularisers, folded in a fixed order (displacement, repulsion, normal) through their row means:
-            # constrain_b (+)= w mean_i out[b,i], g_geo (+)= (w / ne) d(sum_i out[b,i])/dx, UN-scaled like the kNN term's
-            folds = []
-            if self.w_disp != 0:
-                tb = (self.disp_table[0].data_ptr(), self.disp_table[1].data_ptr(), self.disp_table[2])
-                ws = self.reg_ws.data_ptr()
-                check(lib.geoa3_displacement_loss(xe.data_ptr(), self.ori.data_ptr(), self.b, ne, self.k_disp, *tb,
-                                                  t["disp_out"].data_ptr(), ws, sg), "displacement_loss")
-                check(lib.geoa3_displacement_loss_grad(xe.data_ptr(), self.ori.data_ptr(), self.b, ne, self.k_disp, *tb,
-                                                       None, t["disp_grad"].data_ptr(), ws, sg), "displacement_loss_grad")
-                folds.append(("disp", self.w_disp))
-            if self.w_rep != 0 or self.w_cn != 0:
-                if self.reg_share:
-                    reg_d, reg_i = t["knn_d"], knn_adv
-                else:
-                    prior, reg_i = t["reg_knn"][self.reg_cur], t["reg_knn"][1 - self.reg_cur]
-                    check(lib.geoa3_knn_self(xe.data_ptr(), self.b, ne, self.reg_K,
-                                             prior.data_ptr() if self.reg_seeded else None, t["reg_knn_d"].data_ptr(),
-                                             reg_i.data_ptr(), t["reg_scratch"].data_ptr(), 0, sg), "knn_self")
-                    self.reg_seeded = True
-                    self.reg_cur = 1 - self.reg_cur
-                    reg_d = t["reg_knn_d"]
-            if self.w_rep != 0:
-                tb = (reg_d.data_ptr(), reg_i.data_ptr(), self.reg_K)
-                ws = self.reg_ws.data_ptr()
-                check(lib.geoa3_repulsion_loss(xe.data_ptr(), self.b, ne, self.k_rep, self.h_rep, *tb,
-                                               t["rep_out"].data_ptr(), ws, sg), "repulsion_loss")
-                check(lib.geoa3_repulsion_loss_grad(xe.data_ptr(), self.b, ne, self.k_rep, self.h_rep, *tb, None,
-                                                    t["rep_grad"].data_ptr(), ws, sg), "repulsion_loss_grad")
-                folds.append(("rep", self.w_rep))
-            if self.w_cn != 0:
-                # geoa3_kappa takes a table of exactly k + 1 columns and does not look at an index before it follows it: the
-                # columns are copied with every index brought inside the cloud (a point with a non-finite coordinate has
-                # no neighbours, index -1; its own term is NaN, and so is the row's mean).  The gradient kernel reads the
-                # table itself and refuses such a row whole.
-                torch.clamp(reg_i[:, :, :self.k_cn + 1], 0, ne - 1, out=t["cn_knn"])
-                check(lib.geoa3_kappa(xe.data_ptr(), self.nrm.data_ptr(), t["cn_knn"].data_ptr(), None, self.b, ne, ne,
-                                      self.k_cn, t["cn_out"].data_ptr(), sg), "kappa")
-                check(lib.geoa3_corr_normal_loss_grad(xe.data_ptr(), self.nrm.data_ptr(), self.b, ne, self.k_cn,
-                                                      reg_d.data_ptr(), reg_i.data_ptr(), self.reg_K, None,
-                                                      t["cn_grad"].data_ptr(), self.reg_ws.data_ptr(), sg),
-                      "corr_normal_loss_grad")
-                folds.append(("cn", self.w_cn))
-            for name, w in folds:
-                ops.reg_fold_points(t[name + "_out"], t[name + "_grad"], w, self.b, ne, term=t[name + "_loss"],
-                                    constrain=self.geo_out["constrain"], constrain_add=geo_on, g=t["g_geo"], g_add=geo_on,
-                                    stream=sg)
-                constrain = self.geo_out["constrain"]
-                geo_on = True
-            if self.w_uni != 0:   # constrain (+)= w U before the head reads it (no other term on: constrain = w U)
-                ops.uniform_loss(xe, contract=self.uni_contract, workspace=self.uni_ws, out=(t["uni_loss"], t["uni_grad"]))
-                constrain = self.geo_out["constrain"]
-                ops.uniform_fold(t["uni_loss"], None, None, self.w_uni, self.b, ne, constrain=constrain,
-                                 constrain_add=geo_on)
-        late = self.late_join and self.geo_stream is not None
+                self._knn_smoothing(xe, sg, curv if self.knn_share else self.ks_table.search(xe, sg))
+            if self.point_terms:
+                self._point_regularisers(xe, sg, curv)
+            if self.w_uni != 0:
+                self._uniform(xe, sg)
         if self.geo_stream is not None:     # join: the bookkeeping needs the constrain loss, the update the gradient
             self.ev_geo.record(self.geo_stream)
             if not late:
                 main.wait_event(self.ev_geo)
-        if late:   # the classification half of the head now, the victim's backward beside the geometry kernels
-            check(lib.geoa3_attack_head_classify(st, t["logits"].data_ptr(), self._p(vote_logits),
-                                                 self.eval_num if self.sub else 1, t["dlogits"].data_ptr(),
-                                                 t["ok"].data_ptr(), s), "attack_head_classify")
-        else:
-            check(lib.geoa3_attack_head_vote(st, t["logits"].data_ptr(), self._p(vote_logits),
-                                             self.eval_num if self.sub else 1,
-                                             self._p(constrain), x.data_ptr(), step, search_step,
-                                             t["dlogits"].data_ptr(), s), "attack_head")
-        g_cls = None
-        if cfg.cls_loss_type != "None":
-            if self.native:
-                self._native_backward(xe, t["dlogits"], t["g_cls"], s)
+        return self._constrain, self._geo_on
+
+    def _fold(self, sg: int, fold, *args, g: bool = True, **kw):
+        """The one fold step: constrain_b (+)= w term_b (before the head reads it) and, with g, g_geo (+)= w d term_b / dx,
+        through fold(*args, b, ne, ...) on the geometry stream; fold None: the objective, first in the order, has written
+        both itself.  The only place that knows whether either has been written yet.  g_geo stays UN-scaled:
+        attack_update_kernel multiplies all of it by scale_const[b] * inv_global_batch (= c_b / b, the gradient of
+        mean_b(c_b constrain_b)) when it forms g = g_cls + (c_b / b) g_geo, so every term gets that factor there, once."""
+        on = self._geo_on
+        if fold is not None:
+            if g:
+                kw.update(g=self.t["g_geo"], g_add=on)
+            fold(*args, self.b, self.ne, constrain=self.geo_out["constrain"], constrain_add=on, stream=sg, **kw)
+        self._constrain, self._geo_on = self.geo_out["constrain"], on or g
+
+    def _distance_curvature(self, xe: Tensor, sg: int):
+        """The 1-NN tables, the curvature term's K-NN table and the fused distance / Hausdorff / curvature objective
+        (geoA3_attack.py:131-166), which writes constrain and g_geo.  -> the curvature term's table or None"""
+        cfg, t, lib = self.cfg, self.t, self.lib
+        ao = (t["d_ao"], t["i_ao"]) if self.need_nn else (None, None)
+        oa = (t["d_oa"], t["i_oa"]) if self.both else (None, None)
+        if self.need_nn:
+            head = (xe.data_ptr(), self.ori.data_ptr(), self.b, self.ne, self.n)
+            out = [self._p(x) for x in ao + oa]
+            if self.grid_nn1:   # seeded with the tables of the previous iteration (in place)
+                pa, pr = (out[1], out[3]) if self.nn1_seeded else (None, None)
+                fn, policy = ((lib.geoa3_grid_nn1_pair, ()) if self.nn1_policy is None
+                              else (lib.geoa3_debug_grid_nn1_pair, self.nn1_policy))
+                check(fn(*head, pa, pr, *out, *policy, sg), "grid_nn1_pair")
+                self.nn1_seeded = not self.sub
             else:
-                logits_ag.backward(t["dlogits"])
-                t["g_cls"].copy_(x_leaf.grad)
-            g_cls = t["g_cls"]
-        if late:
-            main.wait_event(self.ev_geo)
-            check(lib.geoa3_attack_head_finish(st, t["ok"].data_ptr(), self._p(constrain), x.data_ptr(), step,
-                                               search_step, s), "attack_head_finish")
-        if self.w_uni != 0:   # d mean_b(c_b w U) / dx = w (sum_b c_b) / b dU/dx, unscaled like g_cls (geo stream joined)
-            ops.uniform_fold(t["uni_loss"], t["uni_grad"], t["scale_const"], self.w_uni, self.b, ne, g=t["g_cls"],
-                             g_add=g_cls is not None, stream=s)
-            g_cls = t["g_cls"]
-        g_geo = t["g_geo"] if geo_on else None
-        if self.sub:   # torch.gather's backward (Lib/utility.py:185): scatter the sample's gradient to the full cloud
-            for src, dst in ((g_cls, "g_cls_full"), (g_geo, "g_geo_full")):
-                if src is not None:
-                    check(lib.geoa3_pn2_gather_points_grad(src.data_ptr(), t["sub_idx"].data_ptr(), self.b, 3, self.n,
-                                                           ne, t[dst].data_ptr(), s), "gather_points_grad")
-            g_cls = t["g_cls_full"] if g_cls is not None else None
-            g_geo = t["g_geo_full"] if g_geo is not None else None
-        if self.partial:
-            self.part_t += 1
-            if (step + 1) % 50 != 0:    # the step before a re-draw is never used (periodical_pc = input_all, :260)
-                lr = cfg.lr * (0.9990 ** (self.part_t - 1) if _cfg(cfg, "is_use_lr_scheduler", False) else 1.0)
-                if cfg.optim == "adam":
-                    args = (0, lr / (1.0 - 0.9 ** self.part_t), math.sqrt(1.0 - 0.999 ** self.part_t), 0.0, 0)
-                else:
-                    args = (1, lr, 1.0, 0.9, int(self.part_t == 1))
-                check(lib.geoa3_attack_partial_step(st, self._p(g_cls), self._p(g_geo), t["pidx"].data_ptr(), self.kr,
-                                                    t["periodical"].data_ptr(), t["part"].data_ptr(),
-                                                    t["pm"].data_ptr(), t["pv"].data_ptr(), x.data_ptr(), *args, s),
-                      "attack_partial_step")
-            return None  # the projections / lp_clip act on a padded copy in the reference: no effect (:341-352)
-        return g_cls, g_geo
+                check(lib.geoa3_nn1_pair(*head, *out, sg), "nn1_pair")
+        curv = self.curv_table.search(xe, sg) if self.use_curv else None
+        ops.geo_loss_grad(xe, self.ori, normal_ori=self.nrm if self.use_curv else None, kappa_ori=self.kappa_ori,
+                          d_ao=ao[0], i_ao=ao[1], d_oa=oa[0], i_oa=oa[1], knn_adv=curv[1] if curv else None,
+                          k=self.k if self.use_curv else 0, dis_type=self.dis_type,
+                          single_side=bool(cfg.is_cd_single_side), w_dis=float(cfg.dis_loss_weight),
+                          w_hd=float(cfg.hd_loss_weight), w_curv=float(cfg.curv_loss_weight), out=self.geo_out,
+                          deterministic=self.deterministic, scratch=self.geo_scratch)
+        self._fold(sg, None)
+        return curv
+
+    def _knn_smoothing(self, xe: Tensor, sg: int, table):
+        """S_b = kNN_smoothing_loss(xe)[b] and dS_b/dx (Lib/loss_utils.py:135-149), folded as they are"""
+        t, lib, ws = self.t, self.lib, self.ks_ws.data_ptr()
+        head = (xe.data_ptr(), self.b, self.ne, self.ks, self.knn_coef, table[0].data_ptr(), table[1].data_ptr(), table[2])
+        check(lib.geoa3_knn_smoothing_loss(*head, t["ks_loss"].data_ptr(), None, ws, sg), "knn_smoothing_loss")
+        check(lib.geoa3_knn_smoothing_loss_grad(*head, None, t["ks_grad"].data_ptr(), ws, sg), "knn_smoothing_loss_grad")
+        self._fold(sg, ops.reg_fold, t["ks_loss"], t["ks_grad"], self.w_knn)
+
+    def _point_regularisers(self, xe: Tensor, sg: int, curv):
+        """displacement, repulsion and normal, those that are on: out[b,i] and d(sum_i out[b,i])/dx of each, then folded
+        through their row means: constrain_b (+)= w mean_i out[b,i], g_geo (+)= (w / ne) d(sum_i out[b,i])/dx"""
+        t, lib, b, ne, ws = self.t, self.lib, self.b, self.ne, self.reg_ws.data_ptr()
+        if self.w_disp != 0:   # on the CLEAN cloud's table (setup())
+            clean = self.disp_table
+            head = (xe.data_ptr(), self.ori.data_ptr(), b, ne, self.k_disp, clean[0].data_ptr(), clean[1].data_ptr(), clean[2])
+            check(lib.geoa3_displacement_loss(*head, t["disp_out"].data_ptr(), ws, sg), "displacement_loss")
+            check(lib.geoa3_displacement_loss_grad(*head, None, t["disp_grad"].data_ptr(), ws, sg), "displacement_loss_grad")
+        if self.w_rep != 0 or self.w_cn != 0:
+            reg = curv if self.reg_share else self.reg_table.search(xe, sg)
+            reg_ptrs = (reg[0].data_ptr(), reg[1].data_ptr(), reg[2])
+        if self.w_rep != 0:
+            head = (xe.data_ptr(), b, ne, self.k_rep, self.h_rep, *reg_ptrs)
+            check(lib.geoa3_repulsion_loss(*head, t["rep_out"].data_ptr(), ws, sg), "repulsion_loss")
+            check(lib.geoa3_repulsion_loss_grad(*head, None, t["rep_grad"].data_ptr(), ws, sg), "repulsion_loss_grad")
+        if self.w_cn != 0:
+            # geoa3_kappa takes a table of exactly k + 1 columns and does not look at an index before it follows it: the
+            # columns are copied with every index brought inside the cloud (a point with a non-finite coordinate has
+            # no neighbours, index -1; its own term is NaN, and so is the row's mean).  The gradient kernel reads the
+            # table itself and refuses such a row whole.
+            torch.clamp(reg[1][:, :, :self.k_cn + 1], 0, ne - 1, out=t["cn_knn"])
+            check(lib.geoa3_kappa(xe.data_ptr(), self.nrm.data_ptr(), t["cn_knn"].data_ptr(), None, b, ne, ne, self.k_cn,
+                                  t["cn_out"].data_ptr(), sg), "kappa")
+            check(lib.geoa3_corr_normal_loss_grad(xe.data_ptr(), self.nrm.data_ptr(), b, ne, self.k_cn, *reg_ptrs, None,
+                                                  t["cn_grad"].data_ptr(), ws, sg), "corr_normal_loss_grad")
+        for name, w, _ in self.point_terms:
+            self._fold(sg, ops.reg_fold_points, t[name + "_out"], t[name + "_grad"], w, term=t[name + "_loss"])
+
+    def _uniform(self, xe: Tensor, sg: int):
+        """constrain (+)= w U before the head reads it (no other term on: constrain = w U); dU/dx joins g_cls after the
+        join (_uniform_grad), g_geo is not written"""
+        t = self.t
+        ops.uniform_loss(xe, contract=self.uni_contract, workspace=self.uni_ws, out=(t["uni_loss"], t["uni_grad"]))
+        self._fold(sg, ops.uniform_fold, t["uni_loss"], None, None, self.w_uni, g=False)
+
+    def _head(self, late: bool, vote_logits, constrain, step: int, search_step: int, s: int):
+        t, lib, st, votes = self.t, self.lib, C.byref(self.state), self.eval_num if self.sub else 1
+        if late:   # the classification half of the head now, the victim's backward beside the geometry kernels
+            check(lib.geoa3_attack_head_classify(st, t["logits"].data_ptr(), self._p(vote_logits), votes,
+                                                 t["dlogits"].data_ptr(), t["ok"].data_ptr(), s), "attack_head_classify")
+        else:
+            check(lib.geoa3_attack_head_vote(st, t["logits"].data_ptr(), self._p(vote_logits), votes, self._p(constrain),
+                                             t["x"].data_ptr(), step, search_step, t["dlogits"].data_ptr(), s),
+                  "attack_head_vote")
+
+    def _victim_backward(self, xe: Tensor, autograd, s: int) -> Tensor:
+        t = self.t
+        if self.native:
+            fn = self.lib.geoa3_pn2ssg_backward if self.ssg else self.lib.geoa3_pointnet_backward
+            check(fn(C.byref(self.packed.struct), xe.data_ptr(), t["dlogits"].data_ptr(), xe.shape[0], xe.shape[2],
+                     t["g_cls"].data_ptr(), self.ws.data_ptr(), s), "victim backward")
+        else:
+            logits_ag, x_leaf = autograd
+            logits_ag.backward(t["dlogits"])
+            t["g_cls"].copy_(x_leaf.grad)
+        return t["g_cls"]
+
+    def _head_finish(self, main, constrain, step: int, search_step: int, s: int):
+        """The late join: the rest of the head, once the geometry stream has delivered the constrain loss"""
+        main.wait_event(self.ev_geo)
+        check(self.lib.geoa3_attack_head_finish(C.byref(self.state), self.t["ok"].data_ptr(), self._p(constrain),
+                                                self.t["x"].data_ptr(), step, search_step, s), "attack_head_finish")
+
+    def _uniform_grad(self, g_cls: Optional[Tensor], s: int) -> Tensor:
+        """d mean_b(c_b w U) / dx = w (sum_b c_b) / b dU/dx, unscaled like g_cls (geo stream joined)"""
+        t = self.t
+        ops.uniform_fold(t["uni_loss"], t["uni_grad"], t["scale_const"], self.w_uni, self.b, self.ne, g=t["g_cls"],
+                         g_add=g_cls is not None, stream=s)
+        return t["g_cls"]
+
+    def _scatter_to_full_cloud(self, g_cls: Optional[Tensor], g_geo: Optional[Tensor], s: int):
+        """torch.gather's backward (Lib/utility.py:185): scatter the sample's gradient to the full cloud"""
+        t = self.t
+        for src, dst in ((g_cls, "g_cls_full"), (g_geo, "g_geo_full")):
+            if src is not None:
+                check(self.lib.geoa3_pn2_gather_points_grad(src.data_ptr(), t["sub_idx"].data_ptr(), self.b, 3, self.n,
+                                                            self.ne, t[dst].data_ptr(), s), "gather_points_grad")
+        return (t["g_cls_full"] if g_cls is not None else None), (t["g_geo_full"] if g_geo is not None else None)
+
+    def _partial_update(self, step: int, g_cls: Optional[Tensor], g_geo: Optional[Tensor], s: int) -> None:
+        """--is_partial_var: its own optimiser on the [b,3,knn_range] offset; the step is complete"""
+        t = self.t
+        self.part_t += 1
+        if (step + 1) % 50 != 0:    # the step before a re-draw is never used (periodical_pc = input_all, :260)
+            check(self.lib.geoa3_attack_partial_step(C.byref(self.state), self._p(g_cls), self._p(g_geo),
+                                                     t["pidx"].data_ptr(), self.kr, t["periodical"].data_ptr(),
+                                                     t["part"].data_ptr(), t["pm"].data_ptr(), t["pv"].data_ptr(),
+                                                     t["x"].data_ptr(), *self._optim_scalars(self.part_t - 1), s),
+                  "attack_partial_step")
+        return None  # the projections / lp_clip act on a padded copy in the reference: no effect (:341-352)
+
+    def _optim_scalars(self, done: int):
+        """(optim, step_size, sqrt_bc2, momentum, first) of the step after `done` steps of this optimiser, in double as
+        torch.optim forms them"""
+        cfg = self.cfg
+        lr = cfg.lr * (0.9990 ** done if _cfg(cfg, "is_use_lr_scheduler", False) else 1.0)
+        if cfg.optim == "adam":
+            return 0, lr / (1.0 - 0.9 ** (done + 1)), math.sqrt(1.0 - 0.999 ** (done + 1)), 0.0, 0
+        return 1, lr, 1.0, 0.9, int(done == 0)
 
     def optimiser_step(self, step: int, g_cls: Optional[Tensor], g_geo: Optional[Tensor]):
         """Adam / SGD on the offset with g = g_cls + (scale_const / b) g_geo, then the flag-gated projections
@@ -625,13 +679,7 @@ class AttackRunner:
         st = C.byref(self.state)
         x = t["x"]
         pro_grad = bool(_cfg(cfg, "is_pro_grad", False))
-        # optimiser scalars in double, as torch.optim.Adam forms them
-        lr = cfg.lr * (0.9990 ** step if _cfg(cfg, "is_use_lr_scheduler", False) else 1.0)
-        if cfg.optim == "adam":
-            tt = step + 1
-            step_size, sqrt_bc2, optim = lr / (1.0 - 0.9 ** tt), math.sqrt(1.0 - 0.999 ** tt), 0
-        else:
-            step_size, sqrt_bc2, optim = lr, 1.0, 1
+        optim, step_size, sqrt_bc2, _, _ = self._optim_scalars(step)
         check(lib.geoa3_attack_update(st, self._p(g_cls), self._p(g_geo),
                                       self.ori.data_ptr(), t["offset"].data_ptr(), t["m"].data_ptr(),
                                       t["v"].data_ptr(), x.data_ptr(), optim, step_size, sqrt_bc2,
@@ -650,13 +698,6 @@ class AttackRunner:
                                            t["offset"].data_ptr(), x.data_ptr(), self.b, self.n,
                                            float(_cfg(cfg, "cc_linf", 0.0)), s), "attack_project")
 
-    @property
-    def knn_searches_per_iteration(self) -> int:
-        """geoa3_knn_self launches of one objective(): the curvature term's, the kNN-smoothing term's own and the ONE the
-        repulsion and normal terms share when the curvature term's table does not serve them."""
-        return (int(self.use_curv) + int(self.w_knn != 0 and not self.knn_share) +
-                int((self.w_rep != 0 or self.w_cn != 0) and not self.reg_share))
-
     def end_search_step(self, sync_last_label: Optional[Callable[[Tensor], None]] = None):
         if sync_last_label is not None:
             sync_last_label(self.t["last_label"])
@@ -666,37 +707,24 @@ class AttackRunner:
 
     def info_line(self, search_step, step, i, loader_len) -> str:
         """The reference's progress line (geoA3_attack.py:129,138,154,163,365); the ONLY host sync in the loop."""
-        cfg, t = self.cfg, self.t
-        regs = ((self.w_disp, "disp_loss", "disp_loss"), (self.w_rep, "rep_loss", "rep_loss"),
-                (self.w_cn, "cn_loss", "cnor_loss"))
-        vals = torch.stack([t["loss_n"].mean() * (self.b / float(self.global_batch)), t["cls_loss"].mean(),
-                            self.geo_out["dis_loss"].mean(), self.geo_out["hd_loss"].mean(),
-                            self.geo_out["curv_loss"].mean()] +
-                           ([self.t["uni_loss"]] if self.w_uni != 0 else []) +
-                           ([self.t["ks_loss"].mean()] if self.w_knn != 0 else []) +
-                           [self.t[name].mean() for w, name, _ in regs if w != 0]).tolist()
-        info = "[{5}/{6}][{0}/{1}][{2}/{3}] \t loss: {4:6.4f}\t".format(
-            search_step + 1, cfg.binary_max_steps, step + 1, cfg.iter_max_steps, vals[0], i, loader_len)
-        info += "cls_loss: {0:6.4f}\t".format(vals[1])
-        if cfg.dis_loss_type == "CD":
-            info += "cd_loss: {0:6.4f}\t".format(vals[2])
-        elif cfg.dis_loss_type == "L2":
-            info += "l2_loss: {0:6.4f}\t".format(vals[2])
-        if cfg.hd_loss_weight != 0:
-            info += "hd_loss : {0:6.4f}\t".format(vals[3])
-        if cfg.curv_loss_weight != 0:
-            info += "curv_loss : {0:6.4f}\t".format(vals[4])
-        if self.w_uni != 0:
-            info += "uniform : {0:6.4f}\t".format(vals[5])
-        pos = 5 + int(self.w_uni != 0)
-        if self.w_knn != 0:
-            info += "knn_smooth : {0:6.4f}\t".format(vals[pos])
-            pos += 1
-        for w, _, label in regs:
-            if w != 0:
-                info += "{0} : {1:6.4f}\t".format(label, vals[pos])
-                pos += 1
-        return info
+        cfg, t, go = self.cfg, self.t, self.geo_out
+        tight, spaced = "{0}: {1:6.4f}\t", "{0} : {1:6.4f}\t"
+        # (active, label, format, per-instance values or a scalar), in the order of the line
+        rows = ((True, "loss", tight, t["loss_n"].mean() * (self.b / float(self.global_batch))),
+                (True, "cls_loss", tight, t["cls_loss"]),
+                (cfg.dis_loss_type in ("CD", "L2"), cfg.dis_loss_type.lower() + "_loss", tight, go["dis_loss"]),
+                (cfg.hd_loss_weight != 0, "hd_loss", spaced, go["hd_loss"]),
+                (cfg.curv_loss_weight != 0, "curv_loss", spaced, go["curv_loss"]),
+                (self.w_uni != 0, "uniform", spaced, t.get("uni_loss")),
+                (self.w_knn != 0, "knn_smooth", spaced, t.get("ks_loss")),
+                (self.w_disp != 0, "disp_loss", spaced, t.get("disp_loss")),
+                (self.w_rep != 0, "rep_loss", spaced, t.get("rep_loss")),
+                (self.w_cn != 0, "cnor_loss", spaced, t.get("cn_loss")))
+        rows = [row for row in rows if row[0]]
+        vals = torch.stack([value.mean() for _, _, _, value in rows]).tolist()
+        return "[{4}/{5}][{0}/{1}][{2}/{3}] \t ".format(search_step + 1, cfg.binary_max_steps, step + 1,
+                                                         cfg.iter_max_steps, i, loader_len) + "".join(
+            fmt.format(label, v) for (_, label, fmt, _), v in zip(rows, vals))
 
     def run(self, init_offsets: Optional[Sequence[Tensor]] = None, i: int = 0, loader_len: int = 1,
             verbose: bool = False, sync_last_label: Optional[Callable[[Tensor], None]] = None,
@@ -706,7 +734,6 @@ class AttackRunner:
         jitter_aux(search_step, step) -> (aux1, aux2) [b,ne] or jitter_noise(search_step, step, x) -> [b,3,ne];
         partial_points(search_step, step) -> int (np.random.randint) and partial_inits(search_step, step) ->
         [b,3,knn_range] (nn.init.normal_) for --is_partial_var."""
-        cfg = self.cfg
         self.hooks = dict(hooks or {})
         self._freeze()
         try:
@@ -751,7 +778,7 @@ RUNNER_CFG_FIELDS = ("attack_label", "iter_max_steps", "curv_loss_knn", "curv_lo
                      "is_use_knn_smoothing_loss", "knn_smoothing_loss_weight", "knn_smoothing_k", "knn_threshold_coef",
                      "knn_smoothing_share_table", "displacement_loss_weight", "displacement_loss_knn",
                      "repulsion_loss_weight", "repulsion_loss_knn", "repulsion_loss_h", "corr_normal_loss_weight",
-                     "corr_normal_loss_knn", "reg_share_table")
+                     "corr_normal_loss_knn", "reg_share_table", "is_cd_single_side")
 
 
 def unpack_input(input_data, targeted: bool):

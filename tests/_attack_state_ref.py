@@ -656,7 +656,7 @@ UPDATE_CC = (0.0, 0.004, 5e-7)
 
 
 def adam_scalars(t, lr=0.01):
-    """step_size and sqrt_bc2 of step t (1-based), formed in double as AttackRunner.optimiser_step forms them."""
+    """step_size and sqrt_bc2 of step t (1-based), formed in double as AttackRunner._optim_scalars forms them."""
     return lr / (1.0 - 0.9 ** t), math.sqrt(1.0 - 0.999 ** t)
 
 

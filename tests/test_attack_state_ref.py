@@ -112,7 +112,7 @@ def test_vote_against_torch_mode(E, targeted, C):
 # optimisers against torch.optim in float64
 # ----------------------------------------------------------------------------------------------------------------------
 def test_adam_and_sgd_against_torch_optim():
-    """Eight steps in float64 with the scalars AttackRunner.optimiser_step forms.  The restatement's constants are the
+    """Eight steps in float64 with the scalars AttackRunner._optim_scalars forms.  The restatement's constants are the
     kernel's float32 ones (0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, the float32 step size), each within 2^-24 of torch's
     doubles: a step of size lr agrees to a few 2^-24 lr, eight of them to 8 * 8 * 2^-24 * lr."""
     rng = np.random.default_rng(3)

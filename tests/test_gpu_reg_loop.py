@@ -365,3 +365,29 @@ def test_cli_runs_with_the_flags(tmp_path, monkeypatch):
     rate = float(open(os.path.join(saved_dir, "attack_result.txt")).read().split(":")[1])
     mats = sorted(glob.glob(os.path.join(saved_dir, "Mat", "adv_*.mat")))
     assert len(mats) == round(rate * 250 / 100.0) and len(mats) > 0
+
+
+# ------------------------------------------------------------------------------------------------ 9. the runner cache key
+class _RecordingCfg:
+    """cfg, remembering every attribute name asked of it"""
+
+    def __init__(self, cfg):
+        self._cfg, self._asked = cfg, set()
+
+    def __getattr__(self, name):
+        self._asked.add(name)
+        return getattr(self._cfg, name)
+
+
+@pytest.mark.parametrize("kw", [
+    dict(uniform_loss_weight=1.0, is_use_knn_smoothing_loss=True, knn_smoothing_loss_weight=5.0, displacement_loss_weight=1.0,
+         repulsion_loss_weight=1.0, corr_normal_loss_weight=1.0, is_pro_grad=True),
+    dict(is_subsample_opt=True, npoint=32, eval_num=2, is_pre_jitter_input=True, is_pro_grad=True),
+    dict(is_subsample_opt=True, npoint=32, is_pre_jitter_input=True, is_partial_var=True)], ids=["terms", "sample", "partial"])
+def test_runner_cache_key_names_every_field_the_constructor_reads(net, kw):
+    """attack(..., runner_cache=) keys a runner by RUNNER_CFG_FIELDS: a field AttackRunner.__init__ reads and the tuple
+    lacks would hand a stale runner to the next batch."""
+    from geoa3_amd.attack import RUNNER_CFG_FIELDS, AttackRunner
+    cfg = _RecordingCfg(O.AttackCfg(curv_loss_knn=8, **kw))
+    AttackRunner(net, 2, 64, cfg, torch.device("cuda"))
+    assert cfg._asked and cfg._asked <= set(RUNNER_CFG_FIELDS), sorted(cfg._asked - set(RUNNER_CFG_FIELDS))

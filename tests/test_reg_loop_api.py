@@ -58,5 +58,36 @@ def test_binding_and_header_declare_the_fold():
     assert int(re.search(r"#define GEOA3_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 608
 
 
+def _plan(use_curv=True, k=8, disp=None, rep=None, cn=None, ks=None, **share):
+    """knn_table_plan with a term on where its k is given"""
+    from geoa3_amd.attack import knn_table_plan
+    w = lambda x: 0.0 if x is None else 1.0
+    return knn_table_plan(use_curv, k, w(disp), disp or 16, w(rep), rep or 4, w(cn), cn or 2, w(ks), ks or 5, **share)
+
+
+def test_table_plan_of_the_loop_tests():
+    """The sharing flags, column counts and searches per iteration that tests/test_gpu_reg_loop.py asserts on a runner
+    (sections 5 and 2), from the plan alone."""
+    curv = ("curv", 9)
+    # 5: shared tables, the same with reg_share_table = False, and terms wider than the curvature table
+    assert _plan(disp=8, rep=4, cn=2) == ({"disp": curv, "rep": curv, "cn": curv}, 1)
+    assert _plan(disp=8, rep=4, cn=2, reg_share_table=False) == ({"disp": curv, "rep": ("reg", 5), "cn": ("reg", 5)}, 2)
+    assert _plan(disp=12, rep=12, cn=3, ks=5) == ({"knn": curv, "disp": ("clean", 13), "rep": ("reg", 13),
+                                                   "cn": ("reg", 13)}, 2)
+    # 2: every weight zero, whatever the k's and switches say
+    from geoa3_amd.attack import knn_table_plan
+    assert knn_table_plan(True, 4, 0.0, 8, 0.0, 6, 0.0, 3, 0.0, 5, True, False) == ({}, 1)
+
+
+def test_table_plan_without_the_curvature_table():
+    # no curvature term, every term on: the smoothing term's own search plus ONE for repulsion and normal
+    assert _plan(use_curv=False, k=16, disp=16, rep=4, cn=2, ks=5) == (
+        {"knn": ("own", 6), "disp": ("clean", 17), "rep": ("reg", 5), "cn": ("reg", 5)}, 2)
+    assert _plan(use_curv=False, rep=4) == ({"rep": ("reg", 5)}, 1) and _plan(use_curv=False, cn=3) == ({"cn": ("reg", 4)}, 1)
+    # the smoothing term refused the curvature table, or wider than it
+    assert _plan(ks=5, rep=4, knn_share_table=False) == ({"knn": ("own", 6), "rep": ("curv", 9)}, 2)
+    assert _plan(ks=9) == ({"knn": ("own", 10)}, 2) and _plan(ks=8) == ({"knn": ("curv", 9)}, 1)
+
+
 def test_runner_cache_key_holds_the_new_fields():
     assert set(FIELDS) | {"reg_share_table"} <= set(RUNNER_CFG_FIELDS)

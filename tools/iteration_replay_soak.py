@@ -57,7 +57,8 @@ def replay(runner, iters, step_no, extra=None, progress=None):
             uniq[k] = v
     tensors = uniq
     start = {k: v.clone() for k, v in tensors.items()}
-    attrs = {a: getattr(r, a) for a in ("knn_cur", "knn_seeded", "nn1_seeded", "_ws_fwd_shape") if hasattr(r, a)}
+    attrs = {a: getattr(r, a) for a in ("nn1_seeded", "_ws_fwd_shape") if hasattr(r, a)}
+    tables = [(tb, tb.cur, tb.seeded) for tb in (r.curv_table, r.ks_table, r.reg_table) if tb is not None]
     regions = []
     if getattr(r, "native", False) and not getattr(r, "ssg", False):
         regions = workspace_regions(r.lib, r.b, r.ne, r.classes, r.ws)
@@ -70,6 +71,8 @@ def replay(runner, iters, step_no, extra=None, progress=None):
             v.copy_(start[k])
         for a, val in attrs.items():
             setattr(r, a, val)
+        for tb, cur, seeded in tables:
+            tb.cur, tb.seeded = cur, seeded
         r.step(step_no, 0)
         torch.cuda.synchronize()
         if ref is None:
