@@ -47,7 +47,7 @@ def _record(path, cloud):
 def main(cfg):
     from geoa3_amd import utility as U
     from geoa3_amd.data import AdvModelNet40, synthetic_state_dict
-    from geoa3_amd.pointnet import PointNet
+    from main_attack import load_checkpoint, make_victim
 
     assert cfg.datadir[-1] != "/"
     out_root = os.path.split(cfg.datadir)[0]
@@ -61,18 +61,14 @@ def main(cfg):
 
     dataset = AdvModelNet40(cfg.datadir)
     model_path = os.path.join("Pretrained", cfg.arch, str(cfg.npoint), "model_best.pth.tar")
-    if cfg.arch == "PointNet":
-        net = PointNet(cfg.classes, npoint=cfg.npoint)
-    elif cfg.arch == "PointNetPP":
-        from geoa3_amd.pointnet2 import PointNet2ClassificationSSG
-        net = PointNet2ClassificationSSG(use_xyz=True, use_normal=False)
-    else:
-        raise AssertionError("Not support such arch.")
+    net = make_victim(cfg)
     if os.path.isfile(model_path):
-        net.load_state_dict(torch.load(model_path, map_location="cpu")["state_dict"])
+        load_checkpoint(net, cfg, model_path)
         print("\nSuccessfully load pretrained-model from {}\n".format(model_path))
     elif cfg.synthetic and cfg.arch == "PointNet":
         net.load_state_dict(synthetic_state_dict(cfg.classes, seed=0, device=device))
+    elif cfg.synthetic and cfg.arch == "DGCNN":
+        pass   # the module's own init, seeded above
     else:
         raise FileNotFoundError(model_path)
     net = net.to(device).eval()

@@ -79,6 +79,10 @@ SIGNATURES = {
     "geoa3_knn_scatter_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "geoa3_knn_gather_grad": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_knn_points_grad": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "geoa3_knn_nd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_edge_max": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_edge_max_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "geoa3_edge_max_grad": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "geoa3_kappa": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_geo_loss_grad": (C.c_int, [C.POINTER(GeoArgs), vp]),
     "geoa3_geo_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),

@@ -9,7 +9,8 @@ differentiates through it, a registered autograd formula.  `geoa3_amd.ops.knn_po
 
     geoa3::nn1_pair        knn_points(K=1) both directions            Lib/loss_utils.py:32-33,41,48,70,92
     geoa3::knn             knn_points(K)                              Lib/loss_utils.py:57,77
-    geoa3::knn_points      the pytorch3d operator itself ([b,n,3] arguments, int64 idx, differentiable dists)
+    geoa3::knn_points      the pytorch3d operator itself ([b,n,D] arguments, 1 <= D <= 128, int64 idx, differentiable dists)
+    geoa3::edge_max / _grad     the neighbour half of a fused eval-mode EdgeConv layer and its ordered backward (DGCNN)
     geoa3::knn_points_grad its backward, every point's terms in a fixed order      (pytorch3d knn backward)
     geoa3::knn_gather / _grad   pytorch3d.ops.knn_gather and its ordered backward  Lib/loss_utils.py:58,71,78
     geoa3::kappa           _get_kappa_ori / the forward of _get_kappa_adv   Lib/loss_utils.py:52-82
@@ -104,7 +105,11 @@ def _(adv, ori, normal_ori, kappa_ori, d_ao, i_ao, d_oa, i_oa, knn_adv, dkappa, 
 # ------------------------------------------------------------------------------------------------ pytorch3d.ops.knn_points
 @custom_op("geoa3::knn_points", mutates_args=(), device_types="cuda")
 def knn_points_op(p1: Tensor, p2: Tensor, K: int) -> Tuple[Tensor, Tensor]:
-    """p1 [b,n1,3], p2 [b,n2,3] -> dists [b,n1,K] (squared, ascending), idx int64 [b,n1,K]."""
+    """p1 [b,n1,D], p2 [b,n2,D] -> dists [b,n1,K] (squared, ascending), idx int64 [b,n1,K].  D == 3: the planar searches;
+    any other D: geoa3_knn_nd on the arguments as they are (point-major)."""
+    if p1.shape[2] != 3:
+        d, i = ops.knn_nd(p1.detach().contiguous().float(), p2.detach().contiguous().float(), K)
+        return d, i.long()
     q = p1.detach().permute(0, 2, 1).contiguous().float()
     r = p2.detach().permute(0, 2, 1).contiguous().float()
     if K == 1:
@@ -129,6 +134,15 @@ def _knn_points_setup(ctx, inputs, output):
 def _knn_points_backward(ctx, gd, _gi):
     # pytorch3d's knn backward: dp1 += 2 g (p1 - p2[idx]);  dp2[idx] -= the same, every point's terms in a fixed order
     p1, p2, idx = ctx.saved_tensors
+    if p1.shape[2] != 3:
+        # the autograd of ((p1.unsqueeze(2) - knn_gather(p2, idx))**2).sum(-1), its two sums through the ordered gather
+        # backward: p2's rows by idx, p1's by a table that sends every entry of a query to the query itself
+        b, n1, K = idx.shape
+        t = (2.0 * gd.float()).unsqueeze(-1) * (p1.float().unsqueeze(2) - torch.ops.geoa3.knn_gather(p2.float(), idx))
+        own = torch.arange(n1, device=idx.device, dtype=torch.int64).view(1, n1, 1).expand(b, n1, K).contiguous()
+        g1 = torch.ops.geoa3.knn_gather_grad(t, own, n1)
+        g2 = torch.ops.geoa3.knn_gather_grad(-t, idx, p2.shape[1])
+        return g1.to(p1.dtype), g2.to(p2.dtype), None
     g1, g2 = torch.ops.geoa3.knn_points_grad(p1, p2, idx, gd)
     return g1, g2, None
 
@@ -198,6 +212,50 @@ def _knn_gather_backward(ctx, g):
 
 
 knn_gather_op.register_autograd(_knn_gather_backward, setup_context=_knn_gather_setup)
+
+# ------------------------------------------------------------------------------------------------ fused EdgeConv (DGCNN)
+@custom_op("geoa3::edge_max", mutates_args=(), device_types="cuda")
+def edge_max_op(U: Tensor, V: Tensor, t: Tensor, idx: Tensor) -> Tuple[Tensor, Tensor]:
+    """U, V [b,n,c] float32, t [c], idx int64 [b,n,k] -> (y [b,c,n] = max over the neighbours of lrelu_0.2(U[j] + V[i] + t),
+    arg int32 [b,n,c], the neighbour slot that reaches it).  No gradient flows through idx."""
+    return ops.edge_max(U.detach().contiguous().float(), V.detach().contiguous().float(), t.detach().contiguous().float(),
+                        idx.contiguous())
+
+
+@edge_max_op.register_fake
+def _(U, V, t, idx):
+    b, n, c = U.shape
+    return U.new_empty(b, c, n, dtype=_f32), U.new_empty(b, n, c, dtype=_i32)
+
+
+@custom_op("geoa3::edge_max_grad", mutates_args=(), device_types="cuda")
+def edge_max_grad_op(g: Tensor, y: Tensor, arg: Tensor, idx: Tensor) -> Tuple[Tensor, Tensor]:
+    """The backward of geoa3::edge_max: g, y [b,c,n], arg int32 [b,n,c], idx int64 [b,n,k] -> (d U, d V) [b,n,c], every row
+    of d U summed in ascending (point, slot) order."""
+    return ops.edge_max_grad(g.detach().contiguous().float(), y.contiguous(), arg.contiguous(), idx.contiguous())
+
+
+@edge_max_grad_op.register_fake
+def _(g, y, arg, idx):
+    b, c, n = g.shape
+    return g.new_empty(b, n, c, dtype=_f32), g.new_empty(b, n, c, dtype=_f32)
+
+
+edge_max_grad_op.register_autograd(_no_second_derivative("edge_max_grad"))
+
+
+def _edge_max_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[0], output[1], inputs[3])
+
+
+def _edge_max_backward(ctx, g, _ga):
+    y, arg, idx = ctx.saved_tensors
+    dU, dV = torch.ops.geoa3.edge_max_grad(g, y, arg, idx)
+    dt = dV.sum((0, 1)) if ctx.needs_input_grad[2] else None
+    return dU, dV, dt, None
+
+
+edge_max_op.register_autograd(_edge_max_backward, setup_context=_edge_max_setup)
 
 # ------------------------------------------------------------------------------------------------ Lib/loss_utils.py
 _KINDS = {"cd": 0, "pcd": 1, "hd": 2, "l2": 3}

@@ -80,6 +80,70 @@ def knn_planar(q: Tensor, r: Tensor, K: int, prior: Optional[Tensor] = None, out
     return d, i
 
 
+def knn_nd(q: Tensor, r: Tensor, K: int, out=None) -> Tuple[Tensor, Tensor]:
+    """geoa3_knn_nd: q [B,Nq,D], r [B,Nr,D] point-major float32, 1 <= D <= 128 -> (dists [B,Nq,K] ascending by (distance,
+    index), idx int32 [B,Nq,K]); the distance is the sequential float32 sum over d, a NaN distance counts as +inf."""
+    B, Nq, D = q.shape
+    Nr = r.shape[1]
+    if r.shape[0] != B or r.shape[2] != D:
+        raise _lib.Geoa3Error("knn_nd: q %s and r %s differ in batch or dimension" % (tuple(q.shape), tuple(r.shape)))
+    if out is None:
+        d = torch.empty(B, Nq, K, device=q.device, dtype=torch.float32)
+        i = torch.empty(B, Nq, K, device=q.device, dtype=torch.int32)
+    else:
+        d, i = out
+    check(_lib.load().geoa3_knn_nd(_p(q, torch.float32), _p(r, torch.float32), B, Nq, Nr, D, int(K), _p(d, torch.float32),
+                                   _p(i, torch.int32), _stream()), "geoa3_knn_nd")
+    return d, i
+
+
+def edge_max(U: Tensor, V: Tensor, t: Tensor, idx: Tensor, out=None) -> Tuple[Tensor, Tensor]:
+    """geoa3_edge_max: U, V [B,N,C] float32, t [C], idx int64 [B,N,k] -> (y [B,C,N], arg int32 [B,N,C]):
+    y = lrelu_0.2(U[idx[i, arg]] + V[i] + t), arg the first slot that maximises U[idx[i, .], c]."""
+    B, N, Cc = U.shape
+    K = idx.shape[2]
+    if tuple(V.shape) != (B, N, Cc) or tuple(t.shape) != (Cc,) or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.Geoa3Error("edge_max: U %s, V %s, t %s, idx %s do not fit" % (tuple(U.shape), tuple(V.shape),
+                                                                                tuple(t.shape), tuple(idx.shape)))
+    if out is None:
+        y = torch.empty(B, Cc, N, device=U.device, dtype=torch.float32)
+        arg = torch.empty(B, N, Cc, device=U.device, dtype=torch.int32)
+    else:
+        y, arg = out
+    check(_lib.load().geoa3_edge_max(_p(U, torch.float32), _p(V, torch.float32), _p(t, torch.float32), _p(idx, torch.int64),
+                                     B, N, Cc, K, _p(y, torch.float32), _p(arg, torch.int32), _stream()), "geoa3_edge_max")
+    return y, arg
+
+
+def edge_max_scratch(B: int, N: int, K: int, device) -> Tensor:
+    """Scratch of edge_max_grad for B clouds of N points with K neighbours each."""
+    nbytes = int(_lib.load().geoa3_edge_max_scratch_bytes(B, N, K))
+    if nbytes < 0:
+        raise _lib.Geoa3Error("edge_max_grad: sizes out of range (B=%d, N=%d, K=%d)" % (B, N, K))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def edge_max_grad(g: Tensor, y: Tensor, arg: Tensor, idx: Tensor, scratch: Optional[Tensor] = None, out=None):
+    """geoa3_edge_max_grad: g, y [B,C,N] float32, arg int32 [B,N,C], idx int64 [B,N,k] -> (dU, dV) [B,N,C]: dV = g times the
+    LeakyReLU slope from the sign of y, dU[j] the sum of the dV[i] whose arg-max neighbour is j, in ascending (i, slot)."""
+    B, Cc, N = g.shape
+    K = idx.shape[2]
+    if tuple(y.shape) != (B, Cc, N) or tuple(arg.shape) != (B, N, Cc) or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.Geoa3Error("edge_max_grad: g %s, y %s, arg %s, idx %s do not fit" % (tuple(g.shape), tuple(y.shape),
+                                                                                       tuple(arg.shape), tuple(idx.shape)))
+    if out is None:
+        dU = torch.empty(B, N, Cc, device=g.device, dtype=torch.float32)
+        dV = torch.empty(B, N, Cc, device=g.device, dtype=torch.float32)
+    else:
+        dU, dV = out
+    if scratch is None:
+        scratch = edge_max_scratch(B, N, K, g.device)
+    check(_lib.load().geoa3_edge_max_grad(_p(g, torch.float32), _p(y, torch.float32), _p(arg, torch.int32),
+                                          _p(idx, torch.int64), B, N, Cc, K, _p(dU, torch.float32), _p(dV, torch.float32),
+                                          _p(scratch), _stream()), "geoa3_edge_max_grad")
+    return dU, dV
+
+
 def knn_self_scratch(B: int, N: int, device) -> Tensor:
     """Scratch buffer of geoa3_knn_self for [B,3,N] clouds."""
     return torch.empty(int(_lib.load().geoa3_knn_self_scratch_bytes(B, N)), dtype=torch.uint8, device=device)
@@ -398,7 +462,7 @@ def reg_fold_points(out: Optional[Tensor], grad: Optional[Tensor], w: float, B: 
 
 
 # ---------------------------------------------------------------------------------------------
-# Operator-level mirror of pytorch3d.ops: [b,n,3] point-major arguments, int64 idx,
+# Operator-level mirror of pytorch3d.ops: [b,n,D] point-major arguments (1 <= D <= 128), int64 idx,
 # differentiable through `dists`.
 # ---------------------------------------------------------------------------------------------
 _KNN = collections.namedtuple("KNN", ["dists", "idx", "knn"])
@@ -415,11 +479,15 @@ def _check_lengths(name: str, lengths, b: int, n: int) -> None:
 
 
 def knn_points(p1: Tensor, p2: Tensor, K: int = 1, return_nn: bool = False, lengths1=None, lengths2=None, **_ignored):
-    """pytorch3d.ops.knn_points(p1 [b,n1,3], p2 [b,n2,3], K) -> KNN(dists, idx, knn).  The gradient through `dists` is
-    summed per point in ascending (query, neighbour) order (geoa3_knn_points_grad): the same bits on every run.
-    return_nn: knn = knn_gather(p2, idx) [b,n1,K,3], differentiable in p2 (None otherwise).  lengths1 / lengths2 other
-    than None or all-full raise Geoa3Error."""
+    """pytorch3d.ops.knn_points(p1 [b,n1,D], p2 [b,n2,D], K) -> KNN(dists, idx, knn).  D == 3: the pruned searches of the
+    attack loop; any other 1 <= D <= 128 (n1, n2 <= 8192, K <= min(n2, 64)): geoa3_knn_nd, whose distance is the sequential
+    float32 sum over d and whose ties go to the lower index.  The gradient through `dists` is summed per point in ascending
+    (query, neighbour) order (D == 3: geoa3_knn_points_grad; else the ordered knn_gather backward): the same bits on every
+    run.  return_nn: knn = knn_gather(p2, idx) [b,n1,K,D], differentiable in p2 (None otherwise).  lengths1 / lengths2
+    other than None or all-full raise Geoa3Error."""
     from . import library  # noqa: F401  (registers geoa3::knn_points with its autograd formula)
+    if p1.dim() != 3 or p2.dim() != 3 or p1.shape[2] != p2.shape[2] or p1.shape[0] != p2.shape[0]:
+        raise _lib.Geoa3Error("knn_points: p1 %s and p2 %s must be [b,n1,D] and [b,n2,D]" % (tuple(p1.shape), tuple(p2.shape)))
     _check_lengths("lengths1", lengths1, p1.shape[0], p1.shape[1])
     _check_lengths("lengths2", lengths2, p2.shape[0], p2.shape[1])
     d, idx = torch.ops.geoa3.knn_points(p1, p2, int(K))

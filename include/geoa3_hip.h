@@ -126,6 +126,34 @@ int geoa3_knn_gather_grad(const float* g, const int64_t* idx, int B, int M, int 
 int geoa3_knn_points_grad(const float* p1, const float* p2, const int64_t* idx, const float* gd, int B, int N1, int N2, int K,
                           float* g1, float* g2, void* scratch, void* stream);
 
+/* knn_points in D dimensions (a dynamic-graph network's search in feature space), point-major like the operator:
+ * q [B,Nq,D], r [B,Nr,D] -> dists / idx [B,Nq,K] ascending by (distance, index), exactly equal distances to the lower
+ * index.  The squared distance is the SEQUENTIAL float32 sum acc = fl(acc + fl(fl(q_d - r_d)^2)) over d = 0 .. D-1 from
+ * +0.0, no fused multiply-add: a float32 loop on the CPU reproduces both outputs bit for bit.  A NaN distance (a
+ * non-finite coordinate) is ordered and reported as +inf, so every index lies in [0, Nr).  Exact, all pairs.
+ * Supported: 1 <= D <= GEOA3_KNN_ND_MAX_D, 1 <= K <= min(Nr, GEOA3_KNN_MAX_K), Nq, Nr <= 8192, B <= 65535; anything else
+ * returns GEOA3_EINVAL / GEOA3_ENOSUPPORT and writes nothing. */
+#define GEOA3_KNN_ND_MAX_D 128
+int geoa3_knn_nd(const float* q, const float* r, int B, int Nq, int Nr, int D, int K, float* dists, int32_t* idx,
+                 void* stream);
+
+/* The neighbour half of an eval-mode EdgeConv layer, max_k LeakyReLU_0.2(BN(W [x_j - x_i ; x_i])), with the BatchNorm
+ * folded: the pre-activation of edge (i, j) is U[j] + V[i] + t, U = (s W_a) x, V = (s (W_b - W_a)) x (the caller's GEMMs).
+ * U, V [B,N,C] point-major, t [C], idx int64 [B,N,K] ->
+ *   arg[b,i,c] (int32 [B,N,C]) = the first slot s that maximises U[b, idx[b,i,s], c] (a NaN, once met, stays);
+ *   y[b,c,i]   ([B,C,N])       = lrelu(fl(fl(U[b,idx[b,i,arg],c] + V[b,i,c]) + t[c])),  lrelu(a) = a > 0 ? a : fl(0.2f a).
+ * An index outside [0,N) is never dereferenced: the point's y is NaN, arg its first such slot.  Sizes: N K < 2^31 - 256,
+ * B <= 65535 (GEOA3_EINVAL / GEOA3_ENOSUPPORT otherwise, nothing written). */
+int geoa3_edge_max(const float* U, const float* V, const float* t, const int64_t* idx, int B, int N, int C, int K, float* y,
+                   int32_t* arg, void* stream);
+/* scratch of geoa3_edge_max_grad (the destination lists of idx): bytes, < 0 when the sizes are out of range. */
+int64_t geoa3_edge_max_scratch_bytes(int B, int N, int K);
+/* its backward: g, y [B,C,N], arg, idx as above -> dV[b,i,c] = g'[b,i,c] = y > 0 ? g : fl(0.2f g), and dU[b,j,c] = the
+ * sequential float32 sum, from +0.0, of the g'[b,i,c] with idx[b,i,arg[b,i,c]] == j in ascending (i, slot) order (an index
+ * outside [0,N) gives no term).  No float atomics.  dU, dV [B,N,C]. */
+int geoa3_edge_max_grad(const float* g, const float* y, const int32_t* arg, const int64_t* idx, int B, int N, int C, int K,
+                        float* dU, float* dV, void* scratch, void* stream);
+
 
 /* _get_kappa_ori (Lib/loss_utils.py:52-62) given the self K-NN table knn_idx [B,N,k+1]
  * (column 0, the nearest hit, is dropped exactly as the reference's [:, :, :, 1:] slice):

@@ -20,6 +20,31 @@ import scipy.io as sio
 import torch
 
 
+ARCHS = ("PointNet", "PointNetPP", "DGCNN")   # --arch: the victims of the paper
+
+
+def make_victim(cfg):
+    """The victim module of --arch (on the CPU, default-initialised)."""
+    if cfg.arch == "PointNet":
+        from geoa3_amd.pointnet import PointNet
+        return PointNet(cfg.classes, npoint=cfg.npoint)
+    if cfg.arch == "PointNetPP":   # main_attack.py:139-140: the SSG classifier, 40 classes
+        from geoa3_amd.pointnet2 import PointNet2ClassificationSSG
+        return PointNet2ClassificationSSG(use_xyz=True, use_normal=False)
+    if cfg.arch == "DGCNN":
+        from geoa3_amd.dgcnn import DGCNN
+        return DGCNN(output_channels=cfg.classes)
+    raise AssertionError("Not support such arch.")
+
+
+def load_checkpoint(net, cfg, model_path):
+    """Pretrained/<arch>/<npoint>/model_best.pth.tar into the victim of make_victim: the reference's files hold the weights
+    under 'state_dict' (main_attack.py:144-145); DGCNN.load_state_dict finds them itself (under 'state_dict' or
+    'model_state_dict', or the file is the dict; a `module.` prefix stripped)."""
+    ckpt = torch.load(model_path, map_location="cpu")
+    net.load_state_dict(ckpt if cfg.arch == "DGCNN" else ckpt["state_dict"])
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Point Cloud Attacking")
     # ------------Model-----------------------
@@ -248,12 +273,11 @@ def main(cfg):
 
     from geoa3_amd import attack as geoa3_attack
     from geoa3_amd.data import TEN_LABEL_INDEXES, ModelNet40, synthetic_state_dict, write_synthetic_mat
-    from geoa3_amd.pointnet import PointNet
     from geoa3_amd.utility import estimate_normal_via_ori_normal, farthest_points_sample
 
     if cfg.attack == "GeoA3_mesh":
         raise AssertionError("Not uploaded yet.")          # as the reference (main_attack.py:27-28)
-    if cfg.arch not in ("PointNet", "PointNetPP"):
+    if cfg.arch not in ARCHS:
         raise AssertionError("Not support such arch.")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -305,14 +329,12 @@ def main(cfg):
 
     say("=>Loading model")
     model_path = os.path.join("Pretrained", cfg.arch, str(cfg.npoint), "model_best.pth.tar")
-    if cfg.arch == "PointNet":
-        net = PointNet(cfg.classes, npoint=cfg.npoint)
-    else:   # main_attack.py:139-140: the SSG classifier, 40 classes
-        from geoa3_amd.pointnet2 import PointNet2ClassificationSSG
-        net = PointNet2ClassificationSSG(use_xyz=True, use_normal=False)
+    net = make_victim(cfg)
     if os.path.isfile(model_path):
-        net.load_state_dict(torch.load(model_path, map_location="cpu")["state_dict"])
+        load_checkpoint(net, cfg, model_path)
         say("==>Successfully load pretrained-model from {}".format(model_path))
+    elif cfg.synthetic and cfg.arch == "DGCNN":
+        say("==>No checkpoint at {}: the module's own seeded init (--synthetic)".format(model_path))
     elif cfg.synthetic and cfg.arch == "PointNetPP":
         with torch.no_grad():   # default-initialised modules (seeded above) with non-trivial BatchNorm statistics
             for mod in net.modules():
