@@ -10,6 +10,19 @@ namespace {
 
 constexpr float INF = __builtin_inff();
 
+// The file's rules for what is not a number and what is not an index ("NaN rule"):
+//   * a NaN that enters a kernel leaves it as a NaN in every output it feeds: no fminf / fmaxf may swallow it;
+//   * a K-NN table entry outside [0,N) (geoa3_knn pads with -1 when K > Nr) is never dereferenced: the row that holds
+//     it, in ANY column, comes out as NaN and the other rows keep their bits.
+__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
+__device__ __forceinline__ bool is_nan(float x) { return (geoa3_opaque_bits(x) & 0x7fffffffu) > 0x7f800000u; }
+// Table entry j as a safe index: j itself when it lies in [0,n), else 0 with `bad` raised.
+__device__ __forceinline__ int checked_index(int j, int n, bool& bad) {
+  const bool ok = (unsigned)j < (unsigned)n;
+  bad = bad || !ok;
+  return ok ? j : 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // farthest_points_sample (Lib/utility.py:175-187): m-1 rounds of
 //     dists = min(dists, |p - p_last|);  next = argmax(dists)        (first maximal index)
@@ -179,8 +192,9 @@ __global__ __launch_bounds__(256) void knn_normal_kernel(const float* __restrict
   const float* Nm = normal_ori + (size_t)b * 3 * Nr;
   const int32_t* nb = knn_i + ((size_t)b * Nq + i) * K;
   float sx = 0.f, sy = 0.f, sz = 0.f;
+  bool bad = false;
   for (int m = 0; m < K; ++m) {
-    const int j = nb[m];
+    const int j = checked_index(nb[m], Nr, bad);
     sx += Nm[j];
     sy += Nm[Nr + j];
     sz += Nm[2 * Nr + j];
@@ -192,15 +206,15 @@ __global__ __launch_bounds__(256) void knn_normal_kernel(const float* __restrict
   const float nrm = sqrtf(sx * sx + sy * sy + sz * sz) + 1e-12f;
   float ox = sx / nrm, oy = sy / nrm, oz = sz / nrm;
   if (knn_d[((size_t)b * Nq + i) * K] < 1e-6f) {   // the point did not move: its own original normal
-    const int j = nb[0];
+    const int j = checked_index(nb[0], Nr, bad);
     ox = Nm[j];
     oy = Nm[Nr + j];
     oz = Nm[2 * Nr + j];
   }
   float* O = out + (size_t)b * 3 * Nq;
-  O[i] = ox;
-  O[Nq + i] = oy;
-  O[2 * Nq + i] = oz;
+  O[i] = bad ? quiet_nan() : ox;
+  O[Nq + i] = bad ? quiet_nan() : oy;
+  O[2 * Nq + i] = bad ? quiet_nan() : oz;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -237,12 +251,16 @@ struct LocalFrame {
 
 // Mean and covariance (fp32, factor 1/(k-1)) of the points listed in columns 1..K1-1 of one table row, then the fp64
 // Jacobi: the ONE statement of the neighbourhood's frame, shared by local_frame_kernel and estimate_normal_kernel.
-__device__ __forceinline__ void local_frame_solve(const float* __restrict__ P, const int32_t* __restrict__ nb, int N,
+// Returns false when the row holds an entry outside [0,N), column 0 included: such an entry is read as point 0 and
+// the caller writes NaN instead of the frame.
+__device__ __forceinline__ bool local_frame_solve(const float* __restrict__ P, const int32_t* __restrict__ nb, int N,
                                                   int K1, LocalFrame& f) {
   const int k = K1 - 1;
   float mx = 0.f, my = 0.f, mz = 0.f;
+  bool bad = false;
+  (void)checked_index(nb[0], N, bad);
   for (int m = 1; m <= k; ++m) {
-    const int j = nb[m];
+    const int j = checked_index(nb[m], N, bad);
     mx += P[j];
     my += P[N + j];
     mz += P[2 * N + j];
@@ -253,7 +271,7 @@ __device__ __forceinline__ void local_frame_solve(const float* __restrict__ P, c
   mz *= inv_k;
   float cxx = 0.f, cxy = 0.f, cxz = 0.f, cyy = 0.f, cyz = 0.f, czz = 0.f;
   for (int m = 1; m <= k; ++m) {
-    const int j = nb[m];
+    const int j = checked_index(nb[m], N, bad);
     const float x = P[j] - mx, y = P[N + j] - my, z = P[2 * N + j] - mz;
     cxx += x * x;
     cxy += x * y;
@@ -287,6 +305,7 @@ __device__ __forceinline__ void local_frame_solve(const float* __restrict__ P, c
   f.v[0][0] = v00; f.v[0][1] = v01; f.v[0][2] = v02;
   f.v[1][0] = v10; f.v[1][1] = v11; f.v[1][2] = v12;
   f.v[2][0] = v20; f.v[2][1] = v21; f.v[2][2] = v22;
+  return !bad;
 }
 
 // The sign that makes an eigenvector's largest-magnitude component positive (the first of equal magnitudes).
@@ -302,17 +321,18 @@ __global__ __launch_bounds__(256) void local_frame_kernel(const float* __restric
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   LocalFrame f;
-  local_frame_solve(pc + (size_t)b * 3 * N, knn + ((size_t)b * N + i) * K1, N, K1, f);
+  const bool ok = local_frame_solve(pc + (size_t)b * 3 * N, knn + ((size_t)b * N + i) * K1, N, K1, f);
+  const float nan = quiet_nan();
   const size_t bN = (size_t)b * 3 * N;
-  evals[bN + i] = (float)f.w[0];
-  evals[bN + N + i] = (float)f.w[1];
-  evals[bN + 2 * N + i] = (float)f.w[2];
+  evals[bN + i] = ok ? (float)f.w[0] : nan;
+  evals[bN + N + i] = ok ? (float)f.w[1] : nan;
+  evals[bN + 2 * N + i] = ok ? (float)f.w[2] : nan;
   float* E = evecs + (size_t)b * 9 * N;
   auto put = [&](int e) {
     const double sgn = canonical_sign(f.v[e][0], f.v[e][1], f.v[e][2]);
-    E[(size_t)(e * 3 + 0) * N + i] = (float)(sgn * f.v[e][0]);
-    E[(size_t)(e * 3 + 1) * N + i] = (float)(sgn * f.v[e][1]);
-    E[(size_t)(e * 3 + 2) * N + i] = (float)(sgn * f.v[e][2]);
+    E[(size_t)(e * 3 + 0) * N + i] = ok ? (float)(sgn * f.v[e][0]) : nan;
+    E[(size_t)(e * 3 + 1) * N + i] = ok ? (float)(sgn * f.v[e][1]) : nan;
+    E[(size_t)(e * 3 + 2) * N + i] = ok ? (float)(sgn * f.v[e][2]) : nan;
   };
   put(0);
   put(1);
@@ -371,13 +391,13 @@ __global__ __launch_bounds__(EN_T) void estimate_normal_kernel(const float* __re
   if (i >= N) return;
   const int32_t* nb = knn + ((size_t)b * N + i) * K1;
   LocalFrame f;
-  local_frame_solve(P, nb, N, K1, f);
+  bool bad = !local_frame_solve(P, nb, N, K1, f);
   const double x = f.v[0][0], y = f.v[0][1], z = f.v[0][2];
   double sgn = canonical_sign(x, y, z);
   const float px = P[i], py = P[N + i], pz = P[2 * N + i];
-  const int j0 = nb[0];
-  bool bad = geoa3_nonfinite(px) || geoa3_nonfinite(py) || geoa3_nonfinite(pz) || geoa3_nonfinite(P[j0]) ||
-             geoa3_nonfinite(P[N + j0]) || geoa3_nonfinite(P[2 * N + j0]);
+  const int j0 = checked_index(nb[0], N, bad);
+  bad = bad || geoa3_nonfinite(px) || geoa3_nonfinite(py) || geoa3_nonfinite(pz) || geoa3_nonfinite(P[j0]) ||
+        geoa3_nonfinite(P[N + j0]) || geoa3_nonfinite(P[2 * N + j0]);
   if (orient) {
     const double d = sgn * (x * ((double)px - cx) + y * ((double)py - cy) + z * ((double)pz - cz));
     bad = bad || !(fabs(d) < (double)INF);
@@ -464,6 +484,9 @@ __global__ __launch_bounds__(NC_T) void normalize_cloud_kernel(const float* pts,
 
 // estimate_perpendicular's tail (Lib/utility.py:146-149): clamp(v1*aux1) + clamp(v2*aux2), v1 = eigenvector of the
 // largest eigenvalue, v2 = of the middle one; aux = sigma * randn drawn by the caller.
+// torch.clamp keeps a NaN; fminf(fmaxf(NaN, -c), c) would return -c.
+__device__ __forceinline__ float clamp_keep_nan(float v, float c) { return is_nan(v) ? v : fminf(fmaxf(v, -c), c); }
+
 __global__ __launch_bounds__(256) void perp_jitter_kernel(const float* __restrict__ evecs,
                                                           const float* __restrict__ aux1,
                                                           const float* __restrict__ aux2, int N, float clip,
@@ -474,14 +497,17 @@ __global__ __launch_bounds__(256) void perp_jitter_kernel(const float* __restric
   const float a1 = aux1[(size_t)b * N + i], a2 = aux2[(size_t)b * N + i];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float t1 = fminf(fmaxf(E[(size_t)(6 + c) * N + i] * a1, -clip), clip);
-    const float t2 = fminf(fmaxf(E[(size_t)(3 + c) * N + i] * a2, -clip), clip);
+    const float t1 = clamp_keep_nan(E[(size_t)(6 + c) * N + i] * a1, clip);
+    const float t2 = clamp_keep_nan(E[(size_t)(3 + c) * N + i] * a2, clip);
     out[((size_t)b * 3 + c) * N + i] = t1 + t2;
   }
 }
 
 // compute_data_smoothness.py:63-67: s_i = mean_{m=1..k} |<q_m - p_i, n_i>|, n_i = eigenvector of the SMALLEST
-// eigenvalue; out[b] = max_i s_i (as float bits through an unsigned atomicMax: s_i >= 0).
+// eigenvalue; out[b] = max_i s_i.  The maximum is taken over the float BITS as unsigned integers, inside the wavefront and
+// by the atomicMax: s_i >= 0 orders like its bits, and the bits of a NaN lie above those of +inf, so a NaN s_i (a NaN
+// coordinate or normal, or a row with an entry outside [0,N)) is what out[b] reports.  (A NaN with its sign bit set lies
+// higher still: out[b] is then a NaN all the same; which sign and payload it carries is not specified.)
 __global__ __launch_bounds__(256) void smoothness_kernel(const float* __restrict__ pc, const int32_t* __restrict__ knn,
                                                          const float* __restrict__ evecs, int N, int K1,
                                                          float* __restrict__ per_point, unsigned* __restrict__ out) {
@@ -494,16 +520,19 @@ __global__ __launch_bounds__(256) void smoothness_kernel(const float* __restrict
     const float nx = E[i], ny = E[(size_t)N + i], nz = E[(size_t)2 * N + i];
     const float px = P[i], py = P[N + i], pz = P[2 * N + i];
     const int k = K1 - 1;
+    bool bad = false;
+    (void)checked_index(nb[0], N, bad);
     for (int m = 1; m <= k; ++m) {
-      const int j = nb[m];
+      const int j = checked_index(nb[m], N, bad);
       const float t = (P[j] - px) * nx + (P[N + j] - py) * ny + (P[2 * N + j] - pz) * nz;
       s += fabsf(t);
     }
     s /= (float)k;
+    s = bad ? quiet_nan() : s;
     if (per_point) per_point[(size_t)b * N + i] = s;
   }
-  s = wave_max(s);
-  if ((threadIdx.x & 63) == 0) atomicMax(out + b, __float_as_uint(s));
+  const unsigned top = wave_max_u32(__float_as_uint(s));
+  if ((threadIdx.x & 63) == 0) atomicMax(out + b, top);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -511,6 +540,7 @@ __global__ __launch_bounds__(256) void smoothness_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------
 // dis[b,i] = mean of the K smallest non-self values of sqrt(sum_c (p_j - p_i + 1e-10)^2) (defense.py:27-28; the
 // smallest of the K+1 values, normally the point itself at sqrt(3e-20), is dropped like the reference's [:, :, 1:]).
+// A point with a non-finite coordinate gets NaN, and is no neighbour of any other point (its column is passed over).
 constexpr int SOR_T = 256;
 __global__ __launch_bounds__(SOR_T) void sor_stat_kernel(const float* __restrict__ pc, int N, int K,
                                                          float* __restrict__ dis) {
@@ -556,26 +586,43 @@ __global__ __launch_bounds__(SOR_T) void sor_stat_kernel(const float* __restrict
   if (!live) return;
   float acc = 0.f;
   for (int m = 1; m < K1; ++m) acc += sqrtf(s_best[m * SOR_T + tid]);
-  dis[(size_t)b * N + i] = acc / (float)K;
+  // a non-finite point has no distance to anything (every d above is NaN and was passed over, which would read +inf)
+  const bool lost = geoa3_nonfinite(qx) || geoa3_nonfinite(qy) || geoa3_nonfinite(qz);
+  dis[(size_t)b * N + i] = lost ? quiet_nan() : acc / (float)K;
 }
 
 // Keep-set selection, one workgroup per cloud, indices compacted in ascending order (defense.py:31-45).
 //   mode 0 outliers_fixNum:   keep the N - drop_num smallest dis (equal values: lower index first)
 //   mode 1 outliers_variance: keep dis < mean + alpha * std (unbiased std, float64 accumulation)
+// Mode 0 ranks by a TOTAL order, so exactly N - drop_num elements are kept whatever dis holds: -inf, the finite values
+// (-0 and +0 equal), +inf, then every NaN, equal ranks by index -- a stable sort with NaN last, and the order
+// torch.topk(largest=False) drops in (NaN first).  sel_key maps a float to an unsigned integer that ascends in it.
+__device__ __forceinline__ unsigned sel_key(float d) {
+  unsigned u = geoa3_opaque_bits(d);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;   // NaN, either sign
+  if ((u & 0x7fffffffu) == 0u) u = 0u;                        // -0 -> +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 constexpr int SEL_T = 1024;
 __global__ __launch_bounds__(SEL_T) void sor_select_kernel(const float* __restrict__ dis, int N, int mode, int drop_num,
                                                            float alpha, int32_t* __restrict__ idx_out,
                                                            int32_t* __restrict__ count_out,
                                                            float* __restrict__ stats_out) {
   extern __shared__ __attribute__((aligned(16))) float sel_sm[];
-  float* s_d = sel_sm;   // [N]
+  float* s_d = sel_sm;                                   // [N]: dis (mode 1)
+  unsigned* s_k = reinterpret_cast<unsigned*>(sel_sm);   // ... or its sel_key (mode 0)
   __shared__ double s_red[SEL_T / GEOA3_WAVE];
   __shared__ double s_mean, s_thr;
   __shared__ int s_wcnt[SEL_T / GEOA3_WAVE];
   __shared__ int s_base;
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float* D = dis + (size_t)b * N;
-  for (int i = tid; i < N; i += SEL_T) s_d[i] = D[i];
+  if (mode == 1) {
+    for (int i = tid; i < N; i += SEL_T) s_d[i] = D[i];
+  } else {
+    for (int i = tid; i < N; i += SEL_T) s_k[i] = sel_key(D[i]);
+  }
   if (tid == 0) {
     s_base = 0;
     s_thr = 0.0;
@@ -628,14 +675,14 @@ __global__ __launch_bounds__(SEL_T) void sor_select_kernel(const float* __restri
     const int i = base + tid;
     bool keep = false;
     if (i < N) {
-      const float di = s_d[i];
       if (mode == 1) {
-        keep = di < thr;
+        keep = s_d[i] < thr;
       } else {
+        const unsigned ki = s_k[i];
         int rank = 0;
         for (int j = 0; j < N; ++j) {
-          const float dj = s_d[j];
-          rank += (dj < di || (dj == di && j < i)) ? 1 : 0;
+          const unsigned kj = s_k[j];
+          rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
         }
         keep = rank < keep_n;
       }
@@ -679,18 +726,12 @@ extern "C" int geoa3_fps_sample(const float* pc, int B, int N, int m, const int3
   // 512 threads measured best (1024: 8 % slower, 256: 8-19 %): 0.33 ms for 512 of 1024 points, 1.30 ms for 1024 of 4096
   GEOA3_FPS_LDS_CASE(512, 2) GEOA3_FPS_LDS_CASE(512, 4) GEOA3_FPS_LDS_CASE(512, 8) GEOA3_FPS_LDS_CASE(512, 16)
 #undef GEOA3_FPS_LDS_CASE
-#define GEOA3_FPS_CASE(PPT)                                                                                      \
-  if (N <= PPT * FPS_T) {                                                                                        \
-    hipLaunchKernelGGL(fps_sample_kernel<PPT>, dim3(B), dim3(FPS_T), 0, s, pc, N, m, start, idx, pts);           \
-    GEOA3_CHECK_LAUNCH();                                                                                        \
-    return GEOA3_OK;                                                                                             \
+  // 8192 < N <= 16384: the cloud no longer fits LDS, the register form with 16 points per thread (its only instance)
+  if (N <= 16 * FPS_T) {
+    hipLaunchKernelGGL(fps_sample_kernel<16>, dim3(B), dim3(FPS_T), 0, s, pc, N, m, start, idx, pts);
+    GEOA3_CHECK_LAUNCH();
+    return GEOA3_OK;
   }
-  GEOA3_FPS_CASE(1)
-  GEOA3_FPS_CASE(2)
-  GEOA3_FPS_CASE(4)
-  GEOA3_FPS_CASE(8)
-  GEOA3_FPS_CASE(16)
-#undef GEOA3_FPS_CASE
   return GEOA3_ENOSUPPORT;   // N <= 16384 points per cloud
 }
 

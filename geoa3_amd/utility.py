@@ -76,6 +76,14 @@ def _require_gpu(*tensors: Tensor) -> None:
             raise _lib.Geoa3Error("geoa3_amd.utility has no CPU path: pass GPU tensors")
 
 
+def _require_points(what: str, need: int, have: int) -> None:
+    """A K-NN table wider than the cloud is padded with -1 by the search: the kernels would turn every row into NaN, so
+    the request is refused here, by name."""
+    if need > have:
+        raise _lib.Geoa3Error("%s needs at least %d points per cloud to find its neighbours among, got %d"
+                              % (what, need, have))
+
+
 def farthest_points_normal_sample(obj_points: Tensor, obj_normal: Tensor, num_points: int,
                                   start: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """Lib/utility.py:189-203: ([b,3,n], [b,3,n]) -> ([b,3,num_points], [b,3,num_points]), the normals taken at the
@@ -135,6 +143,7 @@ def estimate_normal(pc: Tensor, k: int, orient: Optional[str] = None, knn_idx: O
         raise ValueError("estimate_normal needs k >= 2 neighbours (a covariance with the factor 1/(k-1))")
     with torch.no_grad():
         b, _, n = pc.shape
+        _require_points("estimate_normal(k=%d)" % k, k + 1, n)
         pc = pc.detach().to(torch.float32).contiguous()
         if knn_idx is None:
             _, knn_idx = knn_planar(pc, pc, k + 1)
@@ -151,6 +160,7 @@ def estimate_normal_via_ori_normal(pc_adv: Tensor, pc_ori: Tensor, normal_ori: T
     """Lib/utility.py:91-108, batched per instance: [b,3,n], [b,3,N], [b,3,N] -> [b,3,n]."""
     b, _, n = pc_adv.shape
     N = pc_ori.shape[2]
+    _require_points("estimate_normal_via_ori_normal(k=%d)" % k, k, N)
     d, i = knn_planar(pc_adv.contiguous(), pc_ori.contiguous(), k)
     out = torch.empty(b, 3, n, device=pc_adv.device, dtype=torch.float32)
     check(_lib.load().geoa3_knn_normal(_p(d), _p(i), _p(normal_ori.contiguous(), torch.float32), b, n, N, k, _p(out),
@@ -162,6 +172,7 @@ def local_frames(pc: Tensor, k: int, knn_idx: Optional[Tensor] = None):
     """Eigen-decomposition of the covariance of the k nearest neighbours of every point: (evals [b,3,n] ascending,
     evecs [b,3(e),3(xyz),n], knn_idx int32 [b,n,k+1])."""
     b, _, n = pc.shape
+    _require_points("local_frames(k=%d)" % k, k + 1, n)
     pc = pc.contiguous()
     if knn_idx is None:
         _, knn_idx = knn_planar(pc, pc, k + 1)
@@ -191,6 +202,7 @@ def estimate_perpendicular(pc: Tensor, k: int, sigma: float = 0.01, clip: float 
 def smoothness(pc: Tensor, k: int = 16, k2: int = 16) -> Tensor:
     """Measurement/compute_data_smoothness.py:37-67 for a batch of clouds [b,3,n] -> [b]."""
     b, _, n = pc.shape
+    _require_points("smoothness(k=%d, k2=%d)" % (k, k2), max(k, k2) + 1, n)
     pc = pc.contiguous()
     _, idx = knn_planar(pc, pc, max(k, k2) + 1)
     idx2 = idx[:, :, : k2 + 1].contiguous()

@@ -577,6 +577,14 @@ int geoa3_pn2ssg_backward(const geoa3_pn2ssg_weights* w, const float* x, const f
 
 /* ------------------------------------------------------------------------------------------
  * Dense-cloud attack path, point-removal defence and smoothness measurement.
+ * Two rules hold for every entry of this section ("NaN rule"):
+ *   - a NaN input is a NaN in every output it feeds (the clamp of geoa3_perp_jitter and the maximum of
+ *     geoa3_smoothness keep it; geoa3_sor_statistic gives NaN for a point with a non-finite coordinate and leaves
+ *     that point out of every other point's neighbours; geoa3_sor_select mode 0 ranks -inf < finite < +inf < NaN,
+ *     equal values by index, and keeps exactly N - drop_num);
+ *   - a K-NN table entry outside [0,N) -- geoa3_knn pads with -1 when K > Nr -- is never dereferenced: a row that
+ *     holds one, in any column, gives NaN in geoa3_local_frames (evals and evecs), geoa3_estimate_normal,
+ *     geoa3_smoothness (per_point, and so out) and geoa3_knn_normal; every other row keeps its bits.
  * ------------------------------------------------------------------------------------------ */
 /* farthest_points_sample, Lib/utility.py:175-187: m-1 rounds of dists = min(dists, |p - p_last|), next = first
  * arg-max.  start [B]: the index the reference draws with torch.randint (:179).  idx [B,m]; pts [B,3,m] (optional)
