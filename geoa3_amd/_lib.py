@@ -149,6 +149,10 @@ SIGNATURES = {
     "geoa3_local_frames": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_estimate_normal": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_normalize_cloud": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "geoa3_mesh_table_bytes": (C.c_int64, [C.c_int64]),
+    "geoa3_mesh_area_table": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp]),
+    "geoa3_mesh_sample": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp,
+                                    vp, vp]),
     "geoa3_perp_jitter": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),
     "geoa3_smoothness": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_sor_statistic": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),

@@ -48,6 +48,9 @@ SLP_FILES = ("pointnet_gemm.hip",)
 FILE_FLAGS = {f: list(_NOSLP) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip") and f not in SLP_FILES}
 for _f in ("pointnet2_sa.hip", "pointnet2_sa2.hip", "pointnet2_sa2b.hip", "geom_filter.hip", "geom_grid.hip"):
     FILE_FLAGS[_f] = ["-fno-honor-nans"] + _NOSLP
+# mesh_sample.hip: its float32 point and float64 area / normal are held to the numpy restatement operation by operation
+# (tests/test_gpu_mesh_kernels.py: points bit for bit), so no multiply may fuse into an add
+FILE_FLAGS["mesh_sample.hip"] = ["-ffp-contract=off"] + _NOSLP
 
 
 def sources():

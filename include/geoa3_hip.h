@@ -635,6 +635,37 @@ int geoa3_sor_select(const float* dis, int B, int N, int mode, int drop_num, flo
                      int32_t* count, float* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh inputs: area-weighted surface sampling of a ragged batch of triangle meshes (Provider/gen_data_mat.py:88-119,
+ * sample_points, which the reference defines and never calls).  Batch layout: verts f32 [total_verts,3]; faces i32
+ * [total_faces,3], indices LOCAL to their mesh; vert_off / face_off i64 [B+1] on the device (mesh b owns
+ * verts[vert_off[b] .. vert_off[b+1]) and faces[face_off[b] .. face_off[b+1])).  The sizes are stated again on the host:
+ * total_verts, total_faces and max_faces = the largest face count of one mesh; the kernels clamp every offset to them.
+ * Limits: max_faces <= 2^22, total_faces < 2^31 (GEOA3_ENOSUPPORT otherwise, nothing launched).
+ * Rules: a face with an index outside [0,V_b) or a non-finite area is never dereferenced, weighs 0, is never selected and
+ * is counted in bad_faces; a mesh of total weight 0 gives NaN points and normals and face_idx -1; so does a sample with a
+ * NaN draw, alone.  Deterministic: integer sums only, repeated calls are bit-identical.
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of the table of geoa3_mesh_area_table (the prefix_sum of gen_data_mat.py:88-119): 8 * total_faces (GEOA3_ENOSUPPORT from 2^31 faces on). */
+int64_t geoa3_mesh_table_bytes(int64_t total_faces);
+/* gen_data_mat.py:88-119, its lines :92-95 (areas, np.cumsum) in exact integers: table u64 [total_faces] = per mesh the inclusive prefix
+ * sum of w_f = rint(A_f / unit), restarting at every mesh; A_f = 0.5 |(b-a) x (c-a)| in double from the float32 vertices,
+ * unit = 2^(e-40) with (m, e) = frexp(the mesh's largest A_f), so w_f <= 2^40 and a mesh's total stays below 2^62.
+ * bad_faces i32 [B].  One workgroup per mesh, no atomics. */
+int geoa3_mesh_area_table(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* face_off,
+                          int B, int64_t total_verts, int64_t total_faces, int64_t max_faces, uint64_t* table,
+                          int32_t* bad_faces, void* stream);
+/* gen_data_mat.py:88-119, its loop :97-115 for S samples of every mesh, from the draws u f32 [B,S,3] in [0,1) the caller makes (:99,
+ * :107-108): with T_b the mesh's last table entry, t = min(T_b - 1, (uint64)((double)u0 * (double)T_b)) and the face is
+ * the first f with table[f] > t (bisect_right, :103); in float32 r1 = u1, r2 = u2, both replaced by 1 - r when
+ * r1 + r2 >= 1, r3 = (1 - r1) - r2, p = (r1 a + r2 b) + r3 c, no contraction (:106-113); the normal is the unit vector of
+ * (b-a) x (c-a) formed in double and rounded once, its sign the winding's.  pts, normals f32 [B,3,S] planar; face_idx
+ * i32 [B,S], local to the mesh.  u0 carries 24 bits: a face below 2^-24 of its mesh's area is hit with a quantised
+ * probability.  B <= 65535. */
+int geoa3_mesh_sample(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* face_off,
+                      const uint64_t* table, const float* u, int B, int S, int64_t total_verts, int64_t total_faces,
+                      int64_t max_faces, float* pts, float* normals, int32_t* face_idx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Uniformity term (Lib/loss_utils.py:151-189, uniform_loss; Attacker/geoA3_attack.py:168-174, --uniform_loss_weight).
  * ------------------------------------------------------------------------------------------ */
 /* loss [1] = U, ONE scalar for the batch: for every p of percentages[num_percentages] (p <- 4p, nsample = int(N p),
