@@ -168,6 +168,7 @@ SIGNATURES = {
     "geoa3_conv1x1": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, vp]),
     "geoa3_debug_pointnet_workspace_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p),
                                                         C.POINTER(C.c_int64), C.c_int]),
+    "geoa3_debug_pointnet_route": (C.c_int, [C.POINTER(PointNetWeights), C.c_int, C.c_int]),
     "geoa3_debug_grid_nn1_pair": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp]),
     "geoa3_debug_knn_self_route": (C.c_int, [C.c_int] * 6),
     "geoa3_debug_geo_route": (C.c_int, [C.POINTER(GeoArgs)]),
@@ -200,7 +201,7 @@ _lib = None
 
 ENOSUPPORT = -3   # GEOA3_ENOSUPPORT
 PN2_CONTRACT = 1   # GEOA3_PN2_CONTRACT
-ABI_VERSION = 608  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
+ABI_VERSION = 609  # GEOA3_ABI_VERSION of include/geoa3_hip.h this file mirrors (tests/test_abi.py holds the two together)
 
 
 class Geoa3Error(RuntimeError):

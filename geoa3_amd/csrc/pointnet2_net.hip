@@ -16,7 +16,7 @@
 //     layer 1 = relu(W_f f + W_x xyz + b);
 //   * level 3's 512 -> 1024 layer runs as two K = 256 products accumulated before the bias / relu / max tail.
 #include <new>
-#include "pointnet_kernels.h"
+#include "pointnet_host.h"
 #include "profile.h"
 
 namespace {
@@ -26,12 +26,6 @@ constexpr float R1 = 0.2f, R2 = 0.4f;
 constexpr int C1 = 128, C2 = 256, C3 = 1024;       // output widths of the three levels
 constexpr int MIN_N = 32;      // (the sampler picks 512 centroids of ANY cloud, repeating points of a small one: sampling_gpu.cu:69-173)
 constexpr int MAX_N = 8192;    // the sampler's register tiling (pointnet2_ops.hip); also keeps N * 3 <= C1 * M1 floats (gx2 in the backward)
-
-#define TRY(expr)               \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 // ---- fragment images of the level-2 / level-3 matrices (launch_frag_image), one buffer: image i at img_off(i), its
 // 1 / scale in the 256 bytes behind it
@@ -74,16 +68,59 @@ int pack_images(const geoa3_pn2ssg_weights& p, void* base, hipStream_t s) {
   return GEOA3_OK;
 }
 
-// (a new field also gets a name in geoa3_debug_pn2ssg_workspace_layout below, in carve()'s order: a static_assert there counts them)
+// The workspace, one line per buffer: type, name, elements (b = B).  Some serve twice: the forward keeps rT (the
+// pre-transformed rows) in `df1` and, with a side queue, the sampler's running distances in `d1`; the backward writes dr over
+// `r` and, with a side queue, the scattered centroid gradient gx2 over `f1`.
+#define PN2_WS(X)                                                                                                          \
+  X(float, xyz, b * N * 3)                                                                                                 \
+  X(int32_t, idx1, b * M1)                                                                                                 \
+  X(float, nx1, b * M1 * 3)                                                                                                \
+  X(int32_t, gidx1, b * M1 * S)                                                                                            \
+  X(float, out1, b * M1 * C1)                                                                                              \
+  X(uint8_t, arg1, b * M1 * C1)                                                                                            \
+  X(float, f1, b * C1 * M1)                                                                                                \
+  X(int32_t, idx2, b * M2)                                                                                                 \
+  X(float, nx2, b * M2 * 3)                                                                                                \
+  X(int32_t, gidx2, b * M2 * S)                                                                                            \
+  X(float, r, b * 128 * M1)                                                                                                \
+  X(float, shift, b * 128 * M2)                                                                                            \
+  /* level 2's backward: rows, entries, tiles (the [B,128,128,64] grouped gradient this slot held until round 5 no longer  \
+     exists) */                                                                                                            \
+  X(float, da0, sa2b_scratch_bytes(B) / sizeof(float))                                                                     \
+  X(float, out2, b * C2 * M2)                                                                                              \
+  X(int32_t, arg2, b * C2 * M2)                                                                                            \
+  X(float, h1, b * 256 * M2)                                                                                               \
+  X(float, h2, b * 512 * M2)                                                                                               \
+  X(float, z3, b * C3 * M2)                                                                                                \
+  X(float, p3, b * C3)                                                                                                     \
+  X(int32_t, arg3, b * C3)                                                                                                 \
+  X(float, q1, b * 512)                                                                                                    \
+  X(float, q2, b * 256)                                                                                                    \
+  /* backward */                                                                                                           \
+  X(float, g256, b * 256)                                                                                                  \
+  X(float, g512, b * 512)                                                                                                  \
+  X(float, g1024, b * C3)                                                                                                  \
+  X(float, dh2, b * 512 * M2)                                                                                              \
+  X(float, dh1, b * 256 * M2)                                                                                              \
+  X(float, dout2, b * C2 * M2)                                                                                             \
+  X(float, dnx2, b * M2 * 3)                                                                                               \
+  /* [B,N] sampler distances | [B,512,64,3] level-1 contributions */                                                       \
+  X(float, d1, b * (size_t)(M1 * S * 3 > MAX_N ? M1 * S * 3 : MAX_N))                                                      \
+  X(float, df1, b * C1 * M1)                                                                                               \
+  X(float, dnx1, b * M1 * 3)                                                                                               \
+  X(float, g1, b * M1 * C1)                                                                                                \
+  X(float, gxyz, b * N * 3)                                                                                                \
+  X(float, gnx1, b * M1 * 3)                                                                                               \
+  /* [B]: the cloud holds a NaN / Inf coordinate (its logits and its input gradient are NaN) */                            \
+  X(int32_t, bad, b)                                                                                                       \
+  /* relu gates of the level-2 activations a0, a1 as bits per row: [B * M2][64][4] */                                      \
+  X(unsigned, m0, b * M2 * S * 4)                                                                                          \
+  X(unsigned, m1, b * M2 * S * 4)                                                                                          \
+  /* fragment images, when the caller passes none (geoa3_pn2ssg_weights::images == NULL) */                                \
+  X(char, images, img_off(IM_COUNT))
+
 struct Ws {
-  float *xyz, *nx1, *out1, *f1, *nx2, *r, *shift, *da0, *out2, *h1, *h2, *z3, *p3, *q1, *q2;
-  int32_t *idx1, *gidx1, *idx2, *gidx2, *arg2, *arg3;
-  uint8_t* arg1;
-  int32_t* bad;    // [B]: the cloud holds a NaN / Inf coordinate (its logits and its input gradient are NaN)
-  // backward
-  float *g256, *g512, *g1024, *dh2, *dh1, *dout2, *dnx2, *d1, *df1, *dnx1, *g1, *gxyz, *gnx1;
-  unsigned *m0, *m1;   // relu gates of the level-2 activations a0, a1 as bits per row: [B * M2][64][4]
-  void* images;   // fragment images, when the caller passes none (geoa3_pn2ssg_weights::images == NULL)
+  PN2_WS(GEOA3_WS_MEMBER)
   size_t total;
 };
 
@@ -91,51 +128,8 @@ Ws carve(void* base, int B, int N) {
   Ws w{};
   size_t off = 0;
   char* p = static_cast<char*>(base);
-  auto take = [&](size_t bytes) {
-    void* r = p ? p + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  const size_t b = (size_t)B, f = sizeof(float);
-  w.xyz = (float*)take(b * N * 3 * f);
-  w.idx1 = (int32_t*)take(b * M1 * 4);
-  w.nx1 = (float*)take(b * M1 * 3 * f);
-  w.gidx1 = (int32_t*)take(b * M1 * S * 4);
-  w.out1 = (float*)take(b * M1 * C1 * f);
-  w.arg1 = (uint8_t*)take(b * M1 * C1);
-  w.f1 = (float*)take(b * C1 * M1 * f);
-  w.idx2 = (int32_t*)take(b * M2 * 4);
-  w.nx2 = (float*)take(b * M2 * 3 * f);
-  w.gidx2 = (int32_t*)take(b * M2 * S * 4);
-  w.r = (float*)take(b * 128 * M1 * f);
-  w.shift = (float*)take(b * 128 * M2 * f);
-  w.da0 = (float*)take(sa2b_scratch_bytes(B));   // level 2's backward: rows, entries, tiles (the [B,128,128,64] grouped gradient this slot held until round 5 no longer exists)
-  w.out2 = (float*)take(b * C2 * M2 * f);
-  w.arg2 = (int32_t*)take(b * C2 * M2 * 4);
-  w.h1 = (float*)take(b * 256 * M2 * f);
-  w.h2 = (float*)take(b * 512 * M2 * f);
-  w.z3 = (float*)take(b * C3 * M2 * f);
-  w.p3 = (float*)take(b * C3 * f);
-  w.arg3 = (int32_t*)take(b * C3 * 4);
-  w.q1 = (float*)take(b * 512 * f);
-  w.q2 = (float*)take(b * 256 * f);
-  w.g256 = (float*)take(b * 256 * f);
-  w.g512 = (float*)take(b * 512 * f);
-  w.g1024 = (float*)take(b * C3 * f);
-  w.dh2 = (float*)take(b * 512 * M2 * f);
-  w.dh1 = (float*)take(b * 256 * M2 * f);
-  w.dout2 = (float*)take(b * C2 * M2 * f);
-  w.dnx2 = (float*)take(b * M2 * 3 * f);
-  w.d1 = (float*)take(b * (size_t)(M1 * S * 3 > MAX_N ? M1 * S * 3 : MAX_N) * f);   // [B,N] sampler distances | [B,512,64,3] level-1 contributions
-  w.df1 = (float*)take(b * C1 * M1 * f);
-  w.dnx1 = (float*)take(b * M1 * 3 * f);
-  w.g1 = (float*)take(b * M1 * C1 * f);
-  w.gxyz = (float*)take(b * N * 3 * f);
-  w.gnx1 = (float*)take(b * M1 * 3 * f);
-  w.bad = (int32_t*)take(b * 4);
-  w.m0 = (unsigned*)take(b * M2 * S * 16);
-  w.m1 = (unsigned*)take(b * M2 * S * 16);
-  w.images = take(img_off(IM_COUNT));
+  const size_t b = (size_t)B;
+  PN2_WS(GEOA3_WS_TAKE)
   w.total = off;
   return w;
 }
@@ -345,18 +339,6 @@ int conv_slice(const float* X, int Kfull, int k0, int K, const Img& W, const flo
   return launch_conv_cm(a, s);
 }
 
-int fc(const float* X, int K, const float* W, const float* bias, float* Y, int Nout, int M, bool relu, const float* Z,
-       hipStream_t s) {
-  FcArgs a{};
-  a.X = X; a.ldX = K;
-  a.W = W; a.ldW = K;
-  a.bias = bias;
-  a.Z = Z; a.ldZ = Nout;
-  a.Y = Y; a.ldY = Nout;
-  a.M = M; a.Nout = Nout; a.K = K; a.relu = relu;
-  return launch_fc(a, s);
-}
-
 }  // namespace
 
 extern "C" int64_t geoa3_pn2ssg_workspace_bytes(int B, int N) {
@@ -369,22 +351,8 @@ extern "C" int geoa3_debug_pn2ssg_workspace_layout(int B, int N, const char** na
   if (B <= 0 || N < MIN_N || N > MAX_N || !names || !offsets) return -1;
   char* const base = reinterpret_cast<char*>(static_cast<uintptr_t>(1) << 40);
   const Ws w = carve(base, B, N);
-  const struct { const char* name; const void* p; } f[] = {
-      {"xyz", w.xyz}, {"idx1", w.idx1}, {"nx1", w.nx1}, {"gidx1", w.gidx1}, {"out1", w.out1}, {"arg1", w.arg1}, {"f1", w.f1},
-      {"idx2", w.idx2}, {"nx2", w.nx2}, {"gidx2", w.gidx2}, {"r", w.r}, {"shift", w.shift}, {"da0", w.da0}, {"out2", w.out2},
-      {"arg2", w.arg2}, {"h1", w.h1}, {"h2", w.h2}, {"z3", w.z3}, {"p3", w.p3}, {"arg3", w.arg3}, {"q1", w.q1}, {"q2", w.q2},
-      {"g256", w.g256}, {"g512", w.g512}, {"g1024", w.g1024}, {"dh2", w.dh2}, {"dh1", w.dh1}, {"dout2", w.dout2},
-      {"dnx2", w.dnx2}, {"d1", w.d1}, {"df1", w.df1}, {"dnx1", w.dnx1}, {"g1", w.g1}, {"gxyz", w.gxyz}, {"gnx1", w.gnx1},
-      {"bad", w.bad}, {"m0", w.m0}, {"m1", w.m1}, {"images", w.images}, {"end", base + w.total}};
-  // every member of Ws is one pointer-sized word (the buffers, then `total`): a field added to the struct without a name here
-  // does not compile
-  static_assert(sizeof(f) / sizeof(f[0]) == sizeof(Ws) / sizeof(void*), "name every field of Ws (and `end` for total)");
-  const int n = (int)(sizeof(f) / sizeof(f[0]));
-  for (int i = 0; i < n && i < cap; ++i) {
-    names[i] = f[i].name;
-    offsets[i] = (int64_t)(static_cast<const char*>(f[i].p) - base);
-  }
-  return n;
+  const WsField f[] = {PN2_WS(GEOA3_WS_FIELD){"end", base + w.total}};
+  return ws_layout(f, (int)(sizeof(f) / sizeof(f[0])), base, names, offsets, cap);
 }
 
 extern "C" int64_t geoa3_pn2ssg_images_bytes(void) { return (int64_t)img_off(IM_COUNT); }

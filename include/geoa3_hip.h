@@ -39,7 +39,7 @@ extern "C" {
 /* The ABI version of this header: bumped on EVERY change of a struct layout or a signature.  geoa3_version() returns the
  * value the library was built with; a binding must refuse a library whose version differs (geoa3_amd/_lib.py does: a
  * stale or variant .so would misread the argument structs silently). */
-#define GEOA3_ABI_VERSION 608
+#define GEOA3_ABI_VERSION 609
 int geoa3_version(void);
 const char* geoa3_strerror(int code);
 
@@ -299,7 +299,10 @@ int geoa3_pointnet_forward(const geoa3_pointnet_weights* w, const float* x, int 
 
 /* dx[B,3,N] = d( sum_b <dlogits[b], logits[b]> ) / d x, for the forward that last filled
  * `workspace`.  Replaces the autograd walk of loss.backward() through the network
- * (Attacker/geoA3_attack.py:326); weight gradients are never formed. */
+ * (Attacker/geoA3_attack.py:326); weight gradients are never formed.
+ * Both directions refuse the same arguments with GEOA3_EINVAL, before any GPU work: a NULL pointer, B or N not positive,
+ * t3.K != 3, t64.K != 64, classes <= 0, a workspace that is not 256-byte aligned (until ABI 609 the backward checked
+ * only the pointers and the sizes). */
 int geoa3_pointnet_backward(const geoa3_pointnet_weights* w, const float* x, const float* dlogits,
                             int B, int N, float* dx, void* workspace, void* stream);
 

@@ -133,6 +133,23 @@ int geoa3_debug_geo_wide(const geoa3_geo_args* args, int ranges, void* stream);
  * of buffers (names[i] are static strings). */
 int geoa3_debug_pointnet_workspace_layout(int B, int N, int classes, const char** names, int64_t* offsets, int cap);
 
+/* The launch sequence geoa3_pointnet_forward / _backward (geoa3_hip.h) would run for these weights and sizes, as a mask of
+ * GEOA3_PN_ROUTE_* bits: the plan both entry points compute once per call and every stage reads.  Or GEOA3_EINVAL where both
+ * refuse the arguments (w NULL, B or N not positive, t3.K != 3, t64.K != 64, classes <= 0).  Only the sizes, w->flags and WHICH
+ * of w5h, w4th, t3.w2th, t64.w2th are given are looked at: no GPU work, no pointer is followed
+ * (tests/test_pointnet_route.py).  Every route returns the same bits as the default one, except SPLIT against fp32. */
+#define GEOA3_PN_ROUTE_SPLIT 1        /* w5h given: split-fp16 operands in every convolution; without it only bits 64 and 256 can be set */
+#define GEOA3_PN_ROUTE_CHAIN 2        /* the trunk's 64-input layers as chain kernels (not GEOA3_PN_NO_CHAIN) */
+#define GEOA3_PN_ROUTE_FUSE_TRUNK 4   /* sparse backward of conv5 + conv4's in one kernel (not GEOA3_PN_NO_FUSE_BWD; w4th given) */
+#define GEOA3_PN_ROUTE_FUSE_T64 8     /* the same for the feature transform's conv3 + conv2 (t64.w2th given) */
+#define GEOA3_PN_ROUTE_FUSE_T3 16     /* ... and the input transform's, with its first layer's backward (t3.w2th given) */
+#define GEOA3_PN_ROUTE_PRE_LISTS 32   /* the forward builds the sparse backward's hit lists: fused backward allowed, N <= 4096,
+                                         not GEOA3_PN_NO_PRE_LISTS */
+#define GEOA3_PN_ROUTE_FC_KSPLIT 64   /* the T-Nets' backward lends G128 to the FC k-split: ceil(B/16)*16*4096 <= B*128*N */
+#define GEOA3_PN_ROUTE_GRAM_F16 128   /* the backward's Gram product on the f16 matrix pipe (with SPLIT) */
+#define GEOA3_PN_ROUTE_CLEAR_KEYS 256 /* the forward zeroes the arg-max keys (not GEOA3_PN_KEYS_CLEAN) */
+int geoa3_debug_pointnet_route(const geoa3_pointnet_weights* w, int B, int N);
+
 /* ------------------------------------------------------------------------------------------
  * The kernels of PointNet++ SSG's second level one at a time (tests/test_gpu_pn2_kernels.py).  Each entry fills the launch
  * arguments the way geoa3_pn2ssg_forward does and starts the kernel; GEOA3_EINVAL for a null pointer or a size outside the

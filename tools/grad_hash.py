@@ -26,7 +26,7 @@ print("PointNet", h.hexdigest())
 from geoa3_amd.pointnet2 import PointNet2ClassificationSSG
 h = hashlib.sha256()
 torch.manual_seed(0)
-net = PointNet2ClassificationSSG(use_xyz=True, use_normal=False).to(dev).eval()
+net = PointNet2ClassificationSSG(use_xyz=True, use_normal=False).to(dev).eval().requires_grad_(False)   # (the victim: no weight gradient)
 for B, N in ((3, 1024), (2, 700), (16, 1024)):
     ori, _ = synthetic_clouds(B, N, seed=B + N)
     x = ori.to(dev).requires_grad_()
