@@ -587,11 +587,10 @@ class AttackRunner:
             check(lib.geoa3_repulsion_loss(*head, t["rep_out"].data_ptr(), ws, sg), "repulsion_loss")
             check(lib.geoa3_repulsion_loss_grad(*head, None, t["rep_grad"].data_ptr(), ws, sg), "repulsion_loss_grad")
         if self.w_cn != 0:
-            # geoa3_kappa takes a table of exactly k + 1 columns and does not look at an index before it follows it: the
-            # columns are copied with every index brought inside the cloud (a point with a non-finite coordinate has
-            # no neighbours, index -1; its own term is NaN, and so is the row's mean).  The gradient kernel reads the
-            # table itself and refuses such a row whole.
-            torch.clamp(reg[1][:, :, :self.k_cn + 1], 0, ne - 1, out=t["cn_knn"])
+            # geoa3_kappa takes a table of exactly k + 1 columns: the columns are copied as they are.  A point with a
+            # non-finite coordinate has no neighbours (index -1, which geoa3_kappa does not follow: its term is NaN, and
+            # so is the row's mean).  The gradient kernel reads the table itself and refuses such a row whole.
+            t["cn_knn"].copy_(reg[1][:, :, :self.k_cn + 1])
             check(lib.geoa3_kappa(xe.data_ptr(), self.nrm.data_ptr(), t["cn_knn"].data_ptr(), None, b, ne, ne, self.k_cn,
                                   t["cn_out"].data_ptr(), sg), "kappa")
             check(lib.geoa3_corr_normal_loss_grad(xe.data_ptr(), self.nrm.data_ptr(), b, ne, self.k_cn, *reg_ptrs, None,

@@ -37,8 +37,11 @@ struct Cfg {
 };
 
 // This file is compiled with -fno-honor-nans (geoa3_amd/build.py): fminf over matrix-core results then is v_min3_f32 without
-// a quieting v_max_f32 v, v, v per operand (15 instead of 8 instructions per 16 accumulators), and no NaN can reach those
-// minima (finite operands of bounded magnitude, see `ok`).  What must SEE a NaN therefore looks at the bits.
+// a quieting v_max_f32 v, v, v per operand (15 instead of 8 instructions per 16 accumulators).  A minimum over accumulators
+// that hold a NaN is whatever the instruction the compiler picked makes of it, so NO caller may build an image from a
+// coordinate that is not finite: search() looks at the bits of every point and query (`pbad`) and geom_grid.hip at the bits
+// of the binned cloud (GridGeom::bad -- its box skips a NaN, so its extent alone does not tell) and of its queries; either
+// then takes the exact sweep at the end of search().  What must SEE a NaN looks at the bits.
 __device__ __forceinline__ float nf_abs_or_inf(float a) {   // |a|, +inf for NaN / inf
   const unsigned u = geoa3_opaque_bits(a) & 0x7fffffffu;
   return u >= 0x7f800000u ? NF_INF : __uint_as_float(u);
@@ -77,6 +80,14 @@ __device__ __forceinline__ void search(const float* __restrict__ P, const float*
     const bool valid = qt[k] < Nq;
     si[k] = prior ? prior[valid ? qt[k] : Nq - 1] : qt[k];
     si[k] = si[k] < 0 ? 0 : (si[k] >= M ? M - 1 : si[k]);
+  }
+  // A partial slice: the slots of the lanes without a query hold a key too -- distance 0, so that their thresholds stay at
+  // -inf when they are tightened from it (mykey[] below); the lanes with a query overwrite theirs with the seed.  Behind a
+  // workgroup-uniform test: a full slice (every slice of a cloud of 1024 points) pays a scalar branch only.
+  if (Nq - q0 < NF_FILTER_SLICE) {
+#pragma unroll
+    for (int k = 0; k < NF_B; ++k)
+      if (kh == 0) s_key[wave * NF_QW + 32 * k + n] = 0ull;
   }
   float sx[NF_B], sy[NF_B], sz[NF_B];
 #pragma unroll

@@ -22,11 +22,17 @@ constexpr float G_INF = __builtin_inff();
 
 struct GridGeom {
   float ox, oy, oz, h, inv_h;
+  int bad;   // a NaN / inf coordinate among the binned points (the box below skips NaN: h alone does not tell)
 };
 
 __device__ __forceinline__ int grid_coord(float f) {
   const int c = (int)floorf(f);
   return c < 0 ? 0 : (c > GG - 1 ? GG - 1 : c);
+}
+
+// NaN / inf among three coordinates, by their bits (this file is compiled with -fno-honor-nans for geom_filter.h)
+__device__ __forceinline__ bool grid_nonfinite3(float x, float y, float z) {
+  return ((int)geoa3_nonfinite(x) | (int)geoa3_nonfinite(y) | (int)geoa3_nonfinite(z)) != 0;
 }
 
 // Bins the M points of P (planar, stride M) into the grid.  On return (after the trailing barrier) s_start[c] ..
@@ -38,6 +44,7 @@ __device__ __forceinline__ GridGeom grid_build(const float* __restrict__ P, int 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float px[PPT], py[PPT], pz[PPT];
   float lox = G_INF, loy = G_INF, loz = G_INF, hix = -G_INF, hiy = -G_INF, hiz = -G_INF;
+  int bad = 0;
 #pragma unroll
   for (int p = 0; p < PPT; ++p) {
     const int i = tid + p * GT;
@@ -45,6 +52,7 @@ __device__ __forceinline__ GridGeom grid_build(const float* __restrict__ P, int 
       px[p] = P[i];
       py[p] = P[M + i];
       pz[p] = P[2 * M + i];
+      bad |= (int)grid_nonfinite3(px[p], py[p], pz[p]);   // (fminf / fmaxf skip a NaN: the box of the finite points)
       lox = fminf(lox, px[p]); hix = fmaxf(hix, px[p]);
       loy = fminf(loy, py[p]); hiy = fmaxf(hiy, py[p]);
       loz = fminf(loz, pz[p]); hiz = fmaxf(hiz, pz[p]);
@@ -60,17 +68,25 @@ __device__ __forceinline__ GridGeom grid_build(const float* __restrict__ P, int 
     float* r = s_red + wave * 6;
     r[0] = lox; r[1] = loy; r[2] = loz; r[3] = hix; r[4] = hiy; r[5] = hiz;
   }
+  int* s_bad = reinterpret_cast<int*>(s_red) + GW * 7;    // [GW] (behind the box and the scan's wave totals)
+  const int wbad = __ballot(bad != 0) != 0ull ? 1 : 0;
+  if (lane == 0) s_bad[wave] = wbad;
   for (int i = tid; i < GC; i += GT) s_fill[i] = 0;
   __syncthreads();
+  bad = 0;
 #pragma unroll
   for (int w = 0; w < GW; ++w) {
     const float* r = s_red + w * 6;
     lox = fminf(lox, r[0]); loy = fminf(loy, r[1]); loz = fminf(loz, r[2]);
     hix = fmaxf(hix, r[3]); hiy = fmaxf(hiy, r[4]); hiz = fmaxf(hiz, r[5]);
+    bad |= s_bad[w];
   }
   GridGeom g;
   g.ox = lox; g.oy = loy; g.oz = loz;
   const float ext = fmaxf(fmaxf(hix - lox, hiy - loy), hiz - loz);
+  // ... or an extent that is not finite (an inf point: h = inf, 1 / h = 0, and a radius of inf times 0 is NaN; finite points
+  // more than FLT_MAX apart).  The callers search such a cloud without the grid
+  g.bad = bad | (int)geoa3_nonfinite(ext);
   g.h = ext * (1.0f / GG) * 1.00001f;      // cubic cells; the far faces lie strictly inside the last cell
   if (!(g.h > 1e-30f)) g.h = 1.0f;         // all points coincide
   g.inv_h = 1.0f / g.h;
@@ -149,11 +165,6 @@ __device__ __forceinline__ void grid_ball(const int* __restrict__ s_start, float
       visit(s_start[col + grid_coord(fz - zr)], s_start[col + grid_coord(fz + zr) + 1]);
     }
   }
-}
-
-// NaN / inf among three coordinates, by their bits (this file is compiled with -fno-honor-nans for geom_filter.h)
-__device__ __forceinline__ bool grid_nonfinite3(float x, float y, float z) {
-  return ((int)geoa3_nonfinite(x) | (int)geoa3_nonfinite(y) | (int)geoa3_nonfinite(z)) != 0;
 }
 
 // One candidate against a query's running (distance, index) minimum -- lexicographic, the un-fused distance of every search.
@@ -418,7 +429,7 @@ __global__ __launch_bounds__(GT, PPT == 1 ? 8 : 4) void grid_nn1_kernel(const fl
   int32_t* iout = (swap ? i_ra : i_ar) + (size_t)b * Nq;
   int* s_start = reinterpret_cast<int*>(g_smem);            // [GC + 1]
   int* s_fill = s_start + GC + 4;                            // [GC]
-  float* s_red = reinterpret_cast<float*>(s_fill + GC);      // [GW*6 + GW]
+  float* s_red = reinterpret_cast<float*>(s_fill + GC);      // [GW*8]: the box per wave, the scan's wave totals, the non-finite flags
   float4* s_p4 = reinterpret_cast<float4*>(s_red + GW * 8);   // [M] (x, y, z, index bits) in cell order
   const GridGeom g = grid_build<GT, PPT>(P, M, s_start, s_fill, s_p4, s_red);
 
@@ -501,7 +512,7 @@ __global__ __launch_bounds__(GT, PPT == 1 ? 8 : 4) void grid_nn1_kernel(const fl
 #pragma unroll
     for (int w = 0; w < GW; ++w) all += s_red[w];
     __syncthreads();
-    if (all > brute_frac * (float)Nq * (float)M) {
+    if (all > brute_frac * (float)Nq * (float)M || g.bad != 0) {   // (g.bad: no walk through a grid of non-finite points)
       if (filter) {
         // ---- through the matrix core (geom_filter.h).  Scale: the cloud's cube (every point within 8 h of its centre) and
         // this workgroup's queries
@@ -514,7 +525,9 @@ __global__ __launch_bounds__(GT, PPT == 1 ? 8 : 4) void grid_nn1_kernel(const fl
           const float dev = fmaxf(fmaxf(nf::nf_abs_or_inf(qx[p] - ccx), nf::nf_abs_or_inf(qy[p] - ccy)), nf::nf_abs_or_inf(qz[p] - ccz));
           m = fmaxf(m, qi[p] >= 0 ? dev : 0.f);
         }
-        m = geoa3_nonfinite(g.h) ? G_INF : m;
+        // a NaN / inf point in the searched cloud (a NaN leaves g.h finite) or a box that is not finite: no images are built
+        // from such coordinates -- the exact sweep of nf::search below
+        m = g.bad != 0 ? G_INF : m;
         m = wave_max(m);
         if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = m;
         __syncthreads();
@@ -659,7 +672,7 @@ __global__ __launch_bounds__(GT, PPT == 1 ? 8 : 4) void grid_nn1_kernel(const fl
 #pragma unroll
       for (int w = 0; w < GW; ++w) all += s_est[w];
       const int nq = Nq - t0 < GT ? Nq - t0 : GT;
-      brute = PPT == 1 && all > brute_frac * (float)nq * (float)M;    // (PPT > 1: decided for all batches above)
+      brute = PPT == 1 && (all > brute_frac * (float)nq * (float)M || g.bad != 0);    // (PPT > 1: decided for all batches above)
     }
     if (brute) {
       // (workgroup-uniform: the cloud once more in INDEX order, strict comparison, no seed -- as above)

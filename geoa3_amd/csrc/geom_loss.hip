@@ -15,11 +15,13 @@ namespace {
 // | < normalize(q - p), n > | summed over the k neighbours listed in nb[1..k] (nb[0] is dropped).
 template <typename Fetch>
 __device__ __forceinline__ float kappa_point(float px, float py, float pz, float nx, float ny, float nz,
-                                             const int32_t* __restrict__ nb, int k, Fetch fetch) {
+                                             const int32_t* __restrict__ nb, int k, int N, int self, Fetch fetch) {
   float acc = 0.f;
   for (int m = 1; m <= k; ++m) {
     float qx, qy, qz;
-    fetch(nb[m], qx, qy, qz);
+    bool oob;
+    fetch(geo_tab_idx(nb[m], N, self, oob), qx, qy, qz);
+    qx = oob ? __builtin_nanf("") : qx;     // an entry outside the cloud: the term is NaN
     const float vx = qx - px, vy = qy - py, vz = qz - pz;
     const float r = sqrtf(vx * vx + vy * vy + vz * vz);
     const float inv = 1.0f / fmaxf(r, NORM_EPS);
@@ -47,8 +49,9 @@ __global__ __launch_bounds__(LDS ? 1024 : 256) void kappa_kernel(const float* __
   }
   if (i >= N) return;
   const float* Nm = normal + (size_t)b * 3 * Nn;
-  const int ni = nn_idx ? nn_idx[(size_t)b * N + i] : i;
-  const float nx = Nm[ni], ny = Nm[Nn + ni], nz = Nm[2 * Nn + ni];
+  bool ni_oob = false;   // (geo_tab_idx: neither nn_idx nor knn_idx is followed outside its cloud; the point's kappa is NaN)
+  const int ni = nn_idx ? geo_tab_idx(nn_idx[(size_t)b * N + i], Nn, 0, ni_oob) : i;
+  const float nx = ni_oob ? __builtin_nanf("") : Nm[ni], ny = Nm[Nn + ni], nz = Nm[2 * Nn + ni];
   const int32_t* nb = knn_idx + ((size_t)b * N + i) * (k + 1);
   const float* Q = LDS ? s_kp : P;
   auto fetch = [&](int j, float& x, float& y, float& z) {
@@ -56,7 +59,7 @@ __global__ __launch_bounds__(LDS ? 1024 : 256) void kappa_kernel(const float* __
     y = Q[N + j];
     z = Q[2 * N + j];
   };
-  kappa[(size_t)b * N + i] = kappa_point(Q[i], Q[N + i], Q[2 * N + i], nx, ny, nz, nb, k, fetch);
+  kappa[(size_t)b * N + i] = kappa_point(Q[i], Q[N + i], Q[2 * N + i], nx, ny, nz, nb, k, N, i, fetch);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -118,7 +121,8 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
     }
     if (do_hd) hd = better(hd, MaxIdx{A.d_ao[bN + i], i});
     if (do_curv) {
-      const int ni = A.i_ao[bN + i];
+      bool ni_oob;   // (geo_tab_idx: an entry of i_ao outside [0, Nr) is not followed, its normal is NaN)
+      const int ni = geo_tab_idx(A.i_ao[bN + i], Nr, 0, ni_oob);
       const float* Nm = A.normal_ori + (size_t)b * 3 * Nr;
       const int32_t* nb = A.knn_adv + (bN + i) * (size_t)(k + 1);
       auto fetch = [&](int j, float& x, float& y, float& z) {
@@ -126,15 +130,16 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
         y = s_ay[j];
         z = s_az[j];
       };
-      const float kap = kappa_point(s_ax[i], s_ay[i], s_az[i], Nm[ni], Nm[Nr + ni], Nm[2 * Nr + ni], nb, k, fetch);
+      const float kap = kappa_point(s_ax[i], s_ay[i], s_az[i], ni_oob ? __builtin_nanf("") : Nm[ni], Nm[Nr + ni], Nm[2 * Nr + ni], nb, k, N, i, fetch);
       const float e = kap - (A.kappa_ori ? A.kappa_ori[bNr + ni] : 0.f);
       s_e[i] = e;
       sum_e2 += e * e;
       if (A.kappa_adv) A.kappa_adv[bN + i] = kap;
     }
   }
-  if (two_side)
-    for (int i = tid; i < Nr; i += GEO_BLOCK) sum_oa += A.d_oa[bNr + i];
+  if (two_side)   // (an entry of i_oa outside [0, N) names no point: its term is NaN)
+    for (int i = tid; i < Nr; i += GEO_BLOCK)
+      sum_oa += (A.i_oa && (unsigned)A.i_oa[bNr + i] >= (unsigned)N) ? __builtin_nanf("") : A.d_oa[bNr + i];
   sum_ao = wave_sum(sum_ao);
   sum_oa = wave_sum(sum_oa);
   sum_e2 = wave_sum(sum_e2);
@@ -193,8 +198,9 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
     const float* Nm = A.normal_ori ? A.normal_ori + (size_t)b * 3 * Nr : nullptr;
     if (do_curv && nrm_in_lds)
       for (int i = tid; i < N; i += GEO_BLOCK) {
-        const int ni = A.i_ao[bN + i];
-        s_nrm[i] = Nm[ni];
+        bool ni_oob;
+        const int ni = geo_tab_idx(A.i_ao[bN + i], Nr, 0, ni_oob);
+        s_nrm[i] = ni_oob ? __builtin_nanf("") : Nm[ni];
         s_nrm[N + i] = Nm[Nr + ni];
         s_nrm[2 * N + i] = Nm[2 * Nr + ni];
       }
@@ -205,8 +211,9 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
         ny = s_nrm[N + i];
         nz = s_nrm[2 * N + i];
       } else {
-        const int ni = A.i_ao[bN + i];
-        nx = Nm[ni];
+        bool ni_oob;
+        const int ni = geo_tab_idx(A.i_ao[bN + i], Nr, 0, ni_oob);
+        nx = ni_oob ? __builtin_nanf("") : Nm[ni];
         ny = Nm[Nr + ni];
         nz = Nm[2 * Nr + ni];
       }
@@ -220,7 +227,7 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
       const float inv = 1.0f / fmaxf(r, NORM_EPS);
       const float ux = vx * inv, uy = vy * inv, uz = vz * inv;
       const float t = ux * nx + uy * ny + uz * nz;
-      const float sg = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
+      const float sg = geo_sign(t);
       const float c = dk * sg * inv;
       if (r >= NORM_EPS) {  // d(v/|v|)/dv = (I - u u^T)/|v|
         dvx = c * (nx - t * ux);
@@ -240,8 +247,10 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
       float gx = 0.f, gy = 0.f, gz = 0.f;
       const float px = s_ax[i], py = s_ay[i], pz = s_az[i];
       if (do_cd || do_hd) {
-        const int j = A.i_ao[bN + i];
-        const float dx = px - ori[j], dy = py - ori[Nr + j], dz = pz - ori[2 * Nr + j];
+        bool j_oob;
+        const int j = geo_tab_idx(A.i_ao[bN + i], Nr, 0, j_oob);
+        const float dx = px - (j_oob ? __builtin_nanf("") : ori[j]), dy = py - (j_oob ? __builtin_nanf("") : ori[Nr + j]),
+                    dz = pz - (j_oob ? __builtin_nanf("") : ori[2 * Nr + j]);
         float c = do_cd ? c_cd : 0.f;
         if (do_hd && i == hd_arg) c += A.w_hd * 2.0f;
         gx += c * dx;
@@ -261,7 +270,9 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
         const float dk = coeff(i);
         for (int m = 1; m <= k; ++m) {
           float dvx, dvy, dvz;
-          pair_grad(px, py, pz, nx, ny, nz, dk, nb[m], dvx, dvy, dvz);
+          bool oob;
+          pair_grad(px, py, pz, nx, ny, nz, dk, geo_tab_idx(nb[m], N, i, oob), dvx, dvy, dvz);
+          if (oob) dvx = dvy = dvz = __builtin_nanf("");   // an entry outside the cloud: the term is NaN
           gx -= dvx;
           gy -= dvy;
           gz -= dvz;
@@ -288,6 +299,7 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
         } else {
           q = A.i_oa[bNr + lo + e];
         }
+        if ((unsigned)q >= (unsigned)N) continue;   // no destination: not followed (the source's own term is NaN, above)
         atomicAdd(&s_cnt[q], 1);
       }
       __syncthreads();
@@ -319,6 +331,7 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
           q = A.i_oa[bNr + lo + e];
           key = lo + e;
         }
+        if ((unsigned)q >= (unsigned)N) continue;
         rlist[atomicAdd(&s_cnt[q], 1)] = key;
       }
       __syncthreads();
@@ -397,6 +410,7 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
     if (two_side && Nr != N) {  // ori point i pulls its nearest adversarial point (dense-cloud path: Nr > N)
       for (int i = tid; i < Nr; i += GEO_BLOCK) {
         const int a = A.i_oa[bNr + i];
+        if ((unsigned)a >= (unsigned)N) continue;   // no destination: not followed (the loss is NaN, above)
         const float dx = s_ax[a] - ori[i], dy = s_ay[a] - ori[Nr + i], dz = s_az[a] - ori[2 * Nr + i];
         atomicAdd(&s_gx[a], c_cd_r * dx);
         atomicAdd(&s_gy[a], c_cd_r * dy);
@@ -407,15 +421,17 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
       float gx = 0.f, gy = 0.f, gz = 0.f;
       const float px = s_ax[i], py = s_ay[i], pz = s_az[i];
       if (do_cd || do_hd) {
-        const int j = A.i_ao[bN + i];
-        const float dx = px - ori[j], dy = py - ori[Nr + j], dz = pz - ori[2 * Nr + j];
+        bool j_oob;
+        const int j = geo_tab_idx(A.i_ao[bN + i], Nr, 0, j_oob);
+        const float dx = px - (j_oob ? __builtin_nanf("") : ori[j]), dy = py - (j_oob ? __builtin_nanf("") : ori[Nr + j]),
+                    dz = pz - (j_oob ? __builtin_nanf("") : ori[2 * Nr + j]);
         float c = do_cd ? c_cd : 0.f;
         if (do_hd && i == hd_arg) c += A.w_hd * 2.0f;
         gx += c * dx;
         gy += c * dy;
         gz += c * dz;
       }
-      if (two_side && Nr == N) {  // ori point i pulls its nearest adversarial point
+      if (two_side && Nr == N && (unsigned)A.i_oa[bN + i] < (unsigned)N) {  // ori point i pulls its nearest adversarial point
         const int a = A.i_oa[bN + i];
         const float dx = s_ax[a] - ori[i], dy = s_ay[a] - ori[Nr + i], dz = s_az[a] - ori[2 * Nr + i];
         atomicAdd(&s_gx[a], c_cd * dx);
@@ -429,19 +445,24 @@ __global__ __launch_bounds__(GEO_BLOCK) void geo_loss_grad_kernel(geoa3_geo_args
         gz += c * (pz - ori[2 * Nr + i]);
       }
       if (do_curv) {
-        const int ni = A.i_ao[bN + i];
+        bool ni_oob;
+        const int ni = geo_tab_idx(A.i_ao[bN + i], Nr, 0, ni_oob);
         const float* Nm = A.normal_ori + (size_t)b * 3 * Nr;
-        const float nx = Nm[ni], ny = Nm[Nr + ni], nz = Nm[2 * Nr + ni];
+        const float nx = ni_oob ? __builtin_nanf("") : Nm[ni], ny = Nm[Nr + ni], nz = Nm[2 * Nr + ni];
         const int32_t* nb = A.knn_adv + (bN + i) * (size_t)(k + 1);
         const float dk = (A.dkappa ? A.dkappa[bN + i] : A.w_curv * invN * 2.0f * s_e[i]) / (float)k;
         for (int m = 1; m <= k; ++m) {
           const int q = nb[m];
+          if ((unsigned)q >= (unsigned)N) {   // an entry outside the cloud: not followed, the centre's term is NaN
+            gx = gy = gz = __builtin_nanf("");
+            continue;
+          }
           const float vx = s_ax[q] - px, vy = s_ay[q] - py, vz = s_az[q] - pz;
           const float r = sqrtf(vx * vx + vy * vy + vz * vz);
           const float inv = 1.0f / fmaxf(r, NORM_EPS);
           const float ux = vx * inv, uy = vy * inv, uz = vz * inv;
           const float t = ux * nx + uy * ny + uz * nz;
-          const float s = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
+          const float s = geo_sign(t);
           const float c = dk * s * inv;
           float dvx, dvy, dvz;
           if (r >= NORM_EPS) {  // d(v/|v|)/dv = (I - u u^T)/|v|
@@ -576,20 +597,24 @@ __global__ __launch_bounds__(GEO_T) void geo_fused_kernel(geoa3_geo_args A, int 
   const bool me_valid = tid < N;
   const int me = me_valid ? tid : N - 1;
   const float px = adv[me], py = adv[N + me], pz = adv[2 * N + me];
-  const int nn = A.i_ao ? A.i_ao[bN + me] : 0;
+  bool nn_oob = false;   // (geo_tab_idx: an entry of i_ao outside [0, Nr) is not followed; its point and normal are NaN)
+  const int nn = A.i_ao ? geo_tab_idx(A.i_ao[bN + me], Nr, 0, nn_oob) : 0;
   const float d_me = A.d_ao ? A.d_ao[bN + me] : 0.f;
   float sum_oa = 0.f;
   int oa_first = 0;
   if (two_side) {
-    for (int i = tid; i < Nr; i += GEO_T) sum_oa += A.d_oa[bNr + i];
-    if (tid < Nr) oa_first = A.i_oa[bNr + tid];
+    for (int i = tid; i < Nr; i += GEO_T) {   // (an entry of i_oa outside [0, N) names no point: its term is NaN)
+      const int q = A.i_oa ? A.i_oa[bNr + i] : 0;
+      sum_oa += (unsigned)q >= (unsigned)N ? __builtin_nanf("") : A.d_oa[bNr + i];
+      if (i == tid) oa_first = q;
+    }
   }
   const float dkap_me = (do_curv && A.dkappa) ? A.dkappa[bN + me] : 0.f;
   float ox = 0.f, oy = 0.f, oz = 0.f;            // the nearest clean point (own Chamfer / Hausdorff term)
   if (do_cd || do_hd) {
-    ox = ori[nn];
-    oy = ori[Nr + nn];
-    oz = ori[2 * Nr + nn];
+    ox = nn_oob ? __builtin_nanf("") : ori[nn];
+    oy = nn_oob ? __builtin_nanf("") : ori[Nr + nn];
+    oz = nn_oob ? __builtin_nanf("") : ori[2 * Nr + nn];
   }
   float lx = 0.f, ly = 0.f, lz = 0.f;            // the clean point of the same index (L2 term)
   if (do_l2) {
@@ -610,7 +635,7 @@ __global__ __launch_bounds__(GEO_T) void geo_fused_kernel(geoa3_geo_args A, int 
     float4 nv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (do_curv) {
       const float* Nm = A.normal_ori + (size_t)b * 3 * Nr;
-      nv = make_float4(Nm[nn], Nm[Nr + nn], Nm[2 * Nr + nn], 0.f);
+      nv = make_float4(nn_oob ? __builtin_nanf("") : Nm[nn], Nm[Nr + nn], Nm[2 * Nr + nn], 0.f);
       kori = A.kappa_ori ? A.kappa_ori[bNr + nn] : 0.f;
     }
     s_p[me] = make_float4(px, py, pz, kori);     // (phase 1 turns .w into the coefficient)
@@ -652,10 +677,13 @@ __global__ __launch_bounds__(GEO_T) void geo_fused_kernel(geoa3_geo_args A, int 
       const int c = c0 + cl;
       const bool cvalid = c < N, active = cvalid && m < k;
       const int cc = cvalid ? c : N - 1;
-      const int q = active ? q_all[p] : cc;
-      const float4 cp = s_p[cc], nv = s_n[cc], qp = s_p[q];
+      bool oob;     // (geom_loss_fix.h: an entry outside the cloud is not followed, the pair's term is NaN)
+      const int q = geo_tab_idx(active ? q_all[p] : cc, N, cc, oob);
+      const float4 cp = s_p[cc], nv = s_n[cc];
+      float4 qp = s_p[q];
+      qp.x = oob ? __builtin_nanf("") : qp.x;
       int slot = -1;
-      if (active && want_grad && (unsigned)(q - r0) < (unsigned)R) {   // the reverse list of q: source c
+      if (active && !oob && want_grad && (unsigned)(q - r0) < (unsigned)R) {   // the reverse list of q: source c
         slot = atomicAdd(&s_cnt[q], 1) & 0x3fffffff;
         if (slot < C) s_rows[(q - r0) * stride + slot] = (uint16_t)c;
       }
@@ -687,7 +715,7 @@ __global__ __launch_bounds__(GEO_T) void geo_fused_kernel(geoa3_geo_args A, int 
   if (two_side && want_grad)       // the clean points: source id N + j in the row of their nearest adversarial point
     for (int j = tid; j < Nr; j += GEO_T) {
       const int q = j == tid ? oa_first : A.i_oa[bNr + j];
-      if ((unsigned)(q - r0) >= (unsigned)R) continue;
+      if ((unsigned)(q - r0) >= (unsigned)R || (unsigned)q >= (unsigned)N) continue;   // (R is rounded up past N)
       const int slot = atomicAdd(&s_cnt[q], 1) & 0x3fffffff;
       if (slot < C) s_rows[(q - r0) * stride + slot] = (uint16_t)(N + j);
       else {
@@ -1008,9 +1036,10 @@ __global__ __launch_bounds__(256) void geo_big_gather_kernel(geoa3_geo_args A, f
   const int N = A.N, Nr = A.Nr > 0 ? A.Nr : N, b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   const size_t bN = (size_t)b * N, bNr = (size_t)b * Nr;
-  const int nn = A.i_ao[bN + i];
+  bool nn_oob;   // (geo_tab_idx: an entry of i_ao outside [0, Nr) is not followed, its normal is NaN)
+  const int nn = geo_tab_idx(A.i_ao[bN + i], Nr, 0, nn_oob);
   const float* Nm = A.normal_ori + bNr * 3;
-  ctr[bN + i] = make_float4(Nm[nn], Nm[Nr + nn], Nm[2 * Nr + nn], A.kappa_ori ? A.kappa_ori[bNr + nn] : 0.f);
+  ctr[bN + i] = make_float4(nn_oob ? __builtin_nanf("") : Nm[nn], Nm[Nr + nn], Nm[2 * Nr + nn], A.kappa_ori ? A.kappa_ori[bNr + nn] : 0.f);
 }
 
 template <int G>
@@ -1086,7 +1115,9 @@ __global__ __launch_bounds__(GB_T) void geo_big_kernel(geoa3_geo_args A, const f
         const bool cvalid = c < N, active = cvalid && lane_on;
         const int cc = cvalid ? c : N - 1;
         const float cx = s_pos[3 * cc], cy = s_pos[3 * cc + 1], cz = s_pos[3 * cc + 2];
-        const float qx = s_pos[3 * q[u]], qy = s_pos[3 * q[u] + 1], qz = s_pos[3 * q[u] + 2];
+        bool oob;   // (geom_loss_fix.h: an entry outside the cloud is not followed, the pair's term is NaN)
+        q[u] = geo_tab_idx(q[u], N, cc, oob);
+        const float qx = oob ? __builtin_nanf("") : s_pos[3 * q[u]], qy = s_pos[3 * q[u] + 1], qz = s_pos[3 * q[u] + 2];
         const float4 nv = cv[u];
         const float vx = qx - cx, vy = qy - cy, vz = qz - cz;
         const float r = GEO_SQRT(vx * vx + vy * vy + vz * vz);
@@ -1099,7 +1130,7 @@ __global__ __launch_bounds__(GB_T) void geo_big_kernel(geoa3_geo_args A, const f
         geo_pair_grad(cx, cy, cz, nv.x, nv.y, nv.z, dk, qx, qy, qz, dvx, dvy, dvz, t2);
         const float sx = group_sum<G>(active ? dvx : 0.f), sy = group_sum<G>(active ? dvy : 0.f),
                     sz = group_sum<G>(active ? dvz : 0.f);
-        if (active && want_grad) geo_fix_add<3>(FX, s_acc, N, pool, s_bad, q[u], dvx, dvy, dvz);
+        if (active && !oob && want_grad) geo_fix_add<3>(FX, s_acc, N, pool, s_bad, q[u], dvx, dvy, dvz);
         if (m == 0 && cvalid) {
           sum_e2 += e * e;
           if (A.kappa_adv) A.kappa_adv[bN + c] = kap;
@@ -1131,6 +1162,7 @@ __global__ __launch_bounds__(GB_T) void geo_big_kernel(geoa3_geo_args A, const f
   if (two_side && want_grad)          // clean point j pulls on its nearest adversarial point
     for (int j = tid; j < Nr; j += GB_T) {
       const int q = A.i_oa[bNr + j];
+      if ((unsigned)q >= (unsigned)N) continue;   // no destination: not followed (the loss is NaN, below)
       geo_fix_add<3>(FX, s_acc, N, pool, s_bad, q, cr * (s_pos[3 * q] - ori[j]), cr * (s_pos[3 * q + 1] - ori[Nr + j]),
                      cr * (s_pos[3 * q + 2] - ori[2 * Nr + j]));
     }
@@ -1149,7 +1181,8 @@ __global__ __launch_bounds__(GB_T) void geo_big_kernel(geoa3_geo_args A, const f
     }
   }
   if (two_side)
-    for (int i = tid; i < Nr; i += GB_T) sum_oa += A.d_oa[bNr + i];
+    for (int i = tid; i < Nr; i += GB_T)
+      sum_oa += (A.i_oa && (unsigned)A.i_oa[bNr + i] >= (unsigned)N) ? __builtin_nanf("") : A.d_oa[bNr + i];
   sum_ao = wave_sum(sum_ao);
   sum_oa = wave_sum(sum_oa);
   sum_e2 = wave_sum(sum_e2);
@@ -1201,8 +1234,10 @@ __global__ __launch_bounds__(GB_T) void geo_big_kernel(geoa3_geo_args A, const f
     const float px = s_pos[3 * i], py = s_pos[3 * i + 1], pz = s_pos[3 * i + 2];
     float gx = 0.f, gy = 0.f, gz = 0.f;
     if (do_cd || do_hd) {
-      const int nn = A.i_ao[bN + i];
-      const float dx = px - ori[nn], dy = py - ori[Nr + nn], dz = pz - ori[2 * Nr + nn];
+      bool nn_oob;
+      const int nn = geo_tab_idx(A.i_ao[bN + i], Nr, 0, nn_oob);
+      const float dx = px - (nn_oob ? __builtin_nanf("") : ori[nn]), dy = py - (nn_oob ? __builtin_nanf("") : ori[Nr + nn]),
+                    dz = pz - (nn_oob ? __builtin_nanf("") : ori[2 * Nr + nn]);
       float c = do_cd ? c_cd : 0.f;
       if (do_hd && i == hd_arg) c += A.w_hd * 2.0f;
       gx += c * dx;

@@ -110,6 +110,16 @@ __device__ __forceinline__ float geo_coef_bound(const geoa3_geo_args& A, int N, 
   return X;
 }
 
+// An entry of the neighbour table before it forms an address.  geoa3_knn / geoa3_knn_self write -1 into the row of a point
+// with a NaN coordinate (and for K > N): outside [0, n) the entry is replaced by `self`, `oob` is set, and the caller gives
+// the neighbour a NaN coordinate, so that the pair's term -- kappa, coefficient, both gradient shares -- counts as NaN.
+__device__ __forceinline__ int geo_tab_idx(int q, int n, int self, bool& oob) {
+  oob = (unsigned)q >= (unsigned)n;
+  return oob ? self : q;
+}
+// the sign of t for d|t|: 0 at 0, and a NaN stays a NaN (with 0 for it a NaN neighbour's pull was 0 under a given dkappa)
+__device__ __forceinline__ float geo_sign(float t) { return t > 0.f ? 1.f : (t < 0.f ? -1.f : (t == t ? 0.f : t)); }
+
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {   // sum over aligned groups of G lanes, in every lane of the group
   if (G >= 2) v += dpp_f32<0xB1, 0xF>(v, 0.f);           // lane ^ 1
@@ -145,7 +155,7 @@ __device__ __forceinline__ void geo_pair_grad(float px, float py, float pz, floa
   const float inv = GEO_RCP(fmaxf(r, NORM_EPS));
   const float ux = vx * inv, uy = vy * inv, uz = vz * inv;
   const float t = __builtin_fmaf(uz, nz, __builtin_fmaf(uy, ny, ux * nx));
-  const float sg = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
+  const float sg = geo_sign(t);
   const float c = dk * sg * inv;
   if (r >= NORM_EPS) {  // d(v/|v|)/dv = (I - u u^T)/|v|
     dvx = c * __builtin_fmaf(-t, ux, nx);

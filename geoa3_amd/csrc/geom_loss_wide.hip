@@ -93,19 +93,26 @@ __global__ __launch_bounds__(GW_T) void geo_wide_pair_kernel(geoa3_geo_args A, f
         const int c = c0 + u * CPP + cl;
         const int cc = c < hi ? c : hi - 1;
         q[u] = (c < hi && lane_on) ? tab[(size_t)c * k1 + 1 + m] : cc;
-        nn[u] = A.i_ao[bN + cc];
+        bool nn_oob;   // (geo_tab_idx: an entry of i_ao outside [0, Nr) is not followed, its normal is NaN: nn = -1 - index)
+        nn[u] = geo_tab_idx(A.i_ao[bN + cc], Nr, 0, nn_oob);
+        nn[u] = nn_oob ? -1 : nn[u];
         dkp[u] = A.dkappa ? A.dkappa[bN + cc] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        cv[u] = make_float4(Nm[nn[u]], Nm[Nr + nn[u]], Nm[2 * Nr + nn[u]], A.kappa_ori ? A.kappa_ori[bNr + nn[u]] : 0.f);
+      {
+        const int ni = nn[u] < 0 ? 0 : nn[u];
+        cv[u] = make_float4(nn[u] < 0 ? __builtin_nanf("") : Nm[ni], Nm[Nr + ni], Nm[2 * Nr + ni], A.kappa_ori ? A.kappa_ori[bNr + ni] : 0.f);
+      }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int c = c0 + u * CPP + cl;
         const bool cvalid = c < hi, active = cvalid && lane_on;
         const int cc = cvalid ? c : hi - 1;
         const float cx = s_pos[3 * cc], cy = s_pos[3 * cc + 1], cz = s_pos[3 * cc + 2];
-        const float qx = s_pos[3 * q[u]], qy = s_pos[3 * q[u] + 1], qz = s_pos[3 * q[u] + 2];
+        bool oob;   // (geom_loss_fix.h: an entry outside the cloud is not followed, the pair's term is NaN)
+        q[u] = geo_tab_idx(q[u], N, cc, oob);
+        const float qx = oob ? __builtin_nanf("") : s_pos[3 * q[u]], qy = s_pos[3 * q[u] + 1], qz = s_pos[3 * q[u] + 2];
         const float4 nv = cv[u];
         const float t = gw_kappa_term(qx - cx, qy - cy, qz - cz, nv.x, nv.y, nv.z);
         const float kap = group_sum<G>(active ? fabsf(t) : 0.f) / (float)k;
@@ -135,7 +142,8 @@ __global__ __launch_bounds__(GW_T) void geo_wide_pair_kernel(geoa3_geo_args A, f
   }
   if (two_side) {   // the clean points in as many chunks as the adversarial ones
     const int per = (Nr + (int)gridDim.x - 1) / (int)gridDim.x, rlo = ch * per, rhi = min(Nr, rlo + per);
-    for (int i = rlo + tid; i < rhi; i += GW_T) sum_oa += A.d_oa[bNr + i];
+    for (int i = rlo + tid; i < rhi; i += GW_T)   // (an entry of i_oa outside [0, N) names no point: its term is NaN)
+      sum_oa += (A.i_oa && (unsigned)A.i_oa[bNr + i] >= (unsigned)N) ? __builtin_nanf("") : A.d_oa[bNr + i];
   }
   sum_ao = wave_sum(sum_ao);
   sum_oa = wave_sum(sum_oa);
@@ -274,14 +282,16 @@ __global__ __launch_bounds__(GW_T) void geo_wide_sum_kernel(geoa3_geo_args A, co
         const bool cvalid = c < N, active = cvalid && lane_on;
         const int cc = cvalid ? c : N - 1;
         const float cx = s_pos[3 * cc], cy = s_pos[3 * cc + 1], cz = s_pos[3 * cc + 2];
-        const float qx = s_pos[3 * q[u]], qy = s_pos[3 * q[u] + 1], qz = s_pos[3 * q[u] + 2];
+        bool oob;
+        q[u] = geo_tab_idx(q[u], N, cc, oob);
+        const float qx = oob ? __builtin_nanf("") : s_pos[3 * q[u]], qy = s_pos[3 * q[u] + 1], qz = s_pos[3 * q[u] + 2];
         const float4 nv = cv[u];
         float dvx, dvy, dvz, t2;
         geo_pair_grad(cx, cy, cz, nv.x, nv.y, nv.z, nv.w, qx, qy, qz, dvx, dvy, dvz, t2);
         const float sx = group_sum<G>(active ? dvx : 0.f), sy = group_sum<G>(active ? dvy : 0.f),
                     sz = group_sum<G>(active ? dvz : 0.f);
         const int ql = q[u] - r0;
-        if (active && (unsigned)ql < (unsigned)Rn) geo_fix_add<3>(FX, s_acc, R, pool, s_bad, ql, dvx, dvy, dvz);
+        if (active && !oob && (unsigned)ql < (unsigned)Rn) geo_fix_add<3>(FX, s_acc, R, pool, s_bad, ql, dvx, dvy, dvz);
         csx[u] = sx;
         csy[u] = sy;
         csz[u] = sz;
@@ -319,8 +329,10 @@ __global__ __launch_bounds__(GW_T) void geo_wide_sum_kernel(geoa3_geo_args A, co
     const float px = s_pos[3 * i], py = s_pos[3 * i + 1], pz = s_pos[3 * i + 2];
     float gx = 0.f, gy = 0.f, gz = 0.f;
     if (do_cd || do_hd) {
-      const int nn = A.i_ao[bN + i];
-      const float dx = px - ori[nn], dy = py - ori[Nr + nn], dz = pz - ori[2 * Nr + nn];
+      bool nn_oob;
+      const int nn = geo_tab_idx(A.i_ao[bN + i], Nr, 0, nn_oob);
+      const float dx = px - (nn_oob ? __builtin_nanf("") : ori[nn]), dy = py - (nn_oob ? __builtin_nanf("") : ori[Nr + nn]),
+                    dz = pz - (nn_oob ? __builtin_nanf("") : ori[2 * Nr + nn]);
       float c = do_cd ? c_cd : 0.f;
       if (do_hd && i == hd_arg) c += A.w_hd * 2.0f;
       gx += c * dx;

@@ -232,7 +232,9 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_kernel(const float* __restrict_
       }
     }
     const bool short_list = live && cnt < K && K <= Nr;
-    if (!__syncthreads_or(short_list)) break;
+    // (after the exact pass a short list stays short -- fewer than K candidates whose distance is not NaN: a NaN query has
+    // none -- and every list is final: falling into the reset below emptied the lists of ALL 256 queries of the workgroup)
+    if (!__syncthreads_or(short_list) || pass == 1) break;
     // some lane was starved by a non-distinct / stale prior: redo exactly, without pruning
     tau = live ? __builtin_inff() : -1.f;
     cnt = 0;

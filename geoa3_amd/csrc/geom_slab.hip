@@ -393,7 +393,7 @@ __global__ __launch_bounds__(SK_BLOCK) void knn_slab_kernel(const float* __restr
     }
     cnt = (int)(aoff >> 10);
     const bool short_list = live && cnt < K && K <= N;
-    if (!__syncthreads_or(short_list)) break;
+    if (!__syncthreads_or(short_list) || pass == 1) break;   // (the exact pass is final: geom_nn.hip, knn_kernel)
     tau = live ? S_INF : -1.f;
     cnt = 0;
     aoff = 4u * tid;
@@ -698,7 +698,7 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI 
    }
     const int cnt = (int)(poff >> 9);
     const bool short_list = live && cnt < K && K <= N;
-    if (!__syncthreads_or(short_list)) break;
+    if (!__syncthreads_or(short_list) || pass == 1) break;   // (the exact pass is final: geom_nn.hip, knn_kernel)
     tau = live ? S_INF : -1.f;
     poff = 2u * tid;
     c_lo = 0;

@@ -401,9 +401,8 @@ def corresponding_normal_loss(adv: Tensor, normal: Tensor, k: int = 2, knn=None,
     B, _, N = adv.shape
     _reg_check(B, N, int(k))
     idx = knn[1][:, :, :k + 1].contiguous() if knn is not None else knn_self_planar(adv, int(k) + 1)[1]
-    # a point with a non-finite coordinate has no neighbours (index -1): the whole instance is NaN, as in the kernels of
-    # csrc/geom_reg.hip, and the table stays inside the cloud
-    idx = idx.clamp(0, N - 1)
+    # a point with a non-finite coordinate has no neighbours (index -1, which geoa3_kappa does not follow: that point's
+    # value is NaN): the whole instance is NaN, as in the kernels of csrc/geom_reg.hip
     out = kappa(adv, normal, idx)
     out = torch.where(_instance_bad(adv).view(B, 1), out.new_full((), float("nan")), out)
     return (out, idx) if want_knn else out

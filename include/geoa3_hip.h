@@ -52,7 +52,11 @@ const char* geoa3_strerror(int code);
  * point of `r` (d_ar, i_ar: [B,Na]) and for every point of `r` its nearest point of `a`
  * (d_ra, i_ra: [B,Nr]).  Replaces the knn_points(K=1) pairs at Lib/loss_utils.py:32-33 (and the
  * repeated adv->ori queries at :48,:70,:92).  d_ra/i_ra may be NULL (one direction only,
- * pseudo_chamfer_loss, Lib/loss_utils.py:41). */
+ * pseudo_chamfer_loss, Lib/loss_utils.py:41).
+ * Non-finite coordinates: the answer is the running minimum from (+inf, 0) over ascending indices with the strict `d < best`,
+ * so a NaN distance (a NaN coordinate; +inf against +inf on one axis) and a +inf distance are never taken, and a query
+ * without a finite distance answers (+inf, 0): every index lies in [0, N) of the searched cloud, a distance is never NaN.
+ * The other instances of the batch keep their bits (tests/_nonfinite_ref.py, tests/test_gpu_nonfinite.py). */
 int geoa3_nn1_pair(const float* a, const float* r, int B, int Na, int Nr,
                    float* d_ar, int32_t* i_ar, float* d_ra, int32_t* i_ra, void* stream);
 
@@ -63,13 +67,22 @@ int geoa3_nn1_pair(const float* a, const float* r, int B, int Na, int Nr,
  * matrix core forms approximate distances of all pairs and only the pairs under the seed's radius (plus a bound on the
  * approximation's error) are evaluated exactly (csrc/geom_filter.hip).  prior_ar [B,Na] / prior_ra [B,Nr] (optional, MAY ALIAS i_ar / i_ra): an index into the
  * searched cloud per query, e.g. last iteration's answer; it only seeds the search radius (default: the point with
- * the query's own index), any value gives the exact result. */
+ * the query's own index), any value gives the exact result.
+ * Non-finite coordinates: the rule of geoa3_nn1_pair, for every prior.  A searched cloud that holds a NaN / inf coordinate, or
+ * whose extent is not finite, is searched without grid and without matrix core (the exact sweep, all pairs); so is a
+ * workgroup of queries that holds one. */
 int geoa3_grid_nn1_pair(const float* a, const float* r, int B, int Na, int Nr, const int32_t* prior_ar,
                         const int32_t* prior_ra, float* d_ar, int32_t* i_ar, float* d_ra, int32_t* i_ra, void* stream);
 
 /* General K (1..GEOA3_KNN_MAX_K): dists/idx [B,Nq,K] ascending by (distance, index).
  * `prior` (optional, [B,Nq,K], int32, K DISTINCT valid indices per query, e.g. the previous
- * iteration's result) only seeds the pruning radius; the result is exact for any prior.
+ * iteration's result) only seeds the pruning radius; the result is exact for any prior (an entry outside [0, Nr) is not
+ * followed: the query is searched without a radius).
+ * Non-finite coordinates: the candidates of a query are the points whose distance is not NaN -- a +inf distance IS one and
+ * sorts behind every finite one, lowest index first; slots beyond the candidates (K > Nr, NaN distances) are (+inf, -1).  A
+ * query with a NaN coordinate therefore comes out as K times (+inf, -1), and a table may hold -1: a consumer must look at an
+ * index before it follows it.  (geoa3_knn_nd has the OTHER rule: a NaN distance counts as +inf and its indices stay in
+ * range.)  Every other row, and every other instance of the batch, keeps its bits.
  * Replaces knn_points(K=k+1) at Lib/loss_utils.py:57,77. */
 #define GEOA3_KNN_MAX_K 64
 int geoa3_knn(const float* q, const float* r, int B, int Nq, int Nr, int K,
@@ -87,6 +100,8 @@ int geoa3_knn(const float* q, const float* r, int B, int Nq, int Nr, int K,
  *            for launches of more than 512 workgroups).
  * Without `prior` or `scratch`, or for N > 8192, it runs the all-pairs kernel.  scratch:
  * geoa3_knn_self_scratch_bytes(B, N) bytes, 256-byte aligned, contents irrelevant.
+ * Non-finite coordinates and a `prior` that holds -1 (last iteration's table of a diverged instance): geoa3_knn's rule and
+ * bits on every route -- the row of a NaN point is K times (+inf, -1), and that point is in no other row.
  * Replaces knn_points(adv, adv, K=k+1) at Lib/loss_utils.py:77. */
 #define GEOA3_KNN_SELF_AUTO 0            /* `method`; any other value behaves as GEOA3_KNN_SELF_SLAB */
 #define GEOA3_KNN_SELF_SLAB 1
@@ -223,6 +238,16 @@ typedef struct geoa3_geo_args {
    * Clouds of 4097..5839 points take the one-workgroup kernel whether `scratch` is given or not. */
   void* scratch;
 } geoa3_geo_args;
+/* The tables and what is not an index.  Every kernel compares every entry it reads from a table with its range before it
+ * forms an address from it: knn_adv and i_oa against [0, N), i_ao against [0, Nr).  (geoa3_knn / geoa3_knn_self write -1
+ * into the row of a point with a NaN coordinate, and for K > N.)  An entry outside is not followed and its term counts as
+ * NaN: for knn_adv the pair's -- kappa_adv and the curvature loss of the instance, the gradient of the row's own point and,
+ * through its coefficient, of the neighbours it does name; for i_ao the point's distance and curvature terms -- its
+ * gradient and kappa_adv; for i_oa the clean point's -- dis_loss and constrain of the instance (no point is pulled).  The
+ * other instances keep their bits (csrc/geom_loss_fix.h, geo_tab_idx; tests/test_gpu_nonfinite.py runs every route on such
+ * tables).  geoa3_kappa treats knn_idx and nn_idx the same way: the point's kappa is NaN.
+ * The Hausdorff point of an instance whose d_ao holds +inf is the LOWEST index among the +inf entries (larger value, then
+ * lower index; a NaN never wins), on every route. */
 int geoa3_geo_loss_grad(const geoa3_geo_args* args, void* stream);
 /* bytes of geoa3_geo_args.scratch for B clouds of N points (k: the neighbours per point; 0 = none) */
 int64_t geoa3_geo_scratch_bytes(int B, int N, int k);

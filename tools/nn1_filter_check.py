@@ -58,6 +58,13 @@ def cases():
     bad[1, 2, 9] = float("inf")
     yield "nan / inf in the searched cloud", ori[:, :, :1024] + 0.01, bad
     yield "nan / inf in the queries", bad, ori[:, :, :1024].contiguous()
+    for n in (1025, 2049, 4096):                 # the grid kernels with two (1025..2048) / four points per thread
+        bad = ori[:, :, :n].clone()
+        bad[0, 0, 3] = float("nan")
+        bad[1, 2, 9] = float("inf")
+        bad[2, :, n - 1] = float("nan")
+        yield "nan / inf in the searched cloud, N=%d" % n, ori[:, :, :n] + 0.01, bad
+        yield "nan / inf in the queries, N=%d" % n, bad, ori[:, :, :n].contiguous()
     yield "1e30 coordinates", 1e30 * (ori[:, :, :1024] + 0.01), 1e30 * ori[:, :, :1024]
 
 
