@@ -114,13 +114,20 @@ def _swap(t):
     return t[:, [0, 2, 1], :].contiguous()
 
 
+def mesh_files(mesh_dir, name, split):
+    """(folder ROOT/<name>/<split>, its *.off / *.obj files, sorted); no files when the folder is missing"""
+    from geoa3_amd import mesh
+    folder = os.path.join(mesh_dir, name, split)
+    files = sorted(f for f in os.listdir(folder) if os.path.splitext(f)[1].lower() in mesh.READERS) \
+        if os.path.isdir(folder) else []
+    return folder, files
+
+
 def mesh_class_clouds(cfg, name, device):
     """Every mesh of ROOT/<name>/<split> -> (points [n,3,npoint], normals, dense points or None, dense normals or None).
     A mesh without any area is left out."""
     from geoa3_amd import mesh
-    folder = os.path.join(cfg.mesh_dir, name, cfg.split)
-    files = sorted(f for f in os.listdir(folder) if os.path.splitext(f)[1].lower() in mesh.READERS) \
-        if os.path.isdir(folder) else []
+    folder, files = mesh_files(cfg.mesh_dir, name, cfg.split)
     if not files:
         return None
     meshes = [mesh.READERS[os.path.splitext(f)[1].lower()](os.path.join(folder, f)) for f in files]

@@ -153,6 +153,18 @@ SIGNATURES = {
     "geoa3_mesh_area_table": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp]),
     "geoa3_mesh_sample": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp,
                                     vp, vp]),
+    # the mesh attack (main_attack.py:27-28, 283-293): pytorch3d's sample_points_from_meshes at a fixed draw with its
+    # pullback, mesh_laplacian_smoothing(method="uniform") and mesh_edge_loss with their gradients
+    "geoa3_mesh_points": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
+    "geoa3_mesh_corner_index": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
+    "geoa3_mesh_points_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "geoa3_mesh_points_lists": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_mesh_points_grad": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_mesh_reg": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp,
+                                 vp, vp, vp, C.c_int, vp]),
+    "geoa3_mesh_reg_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, C.c_float, C.c_float, C.c_int,
+                                      C.c_int, C.c_int, vp, C.c_int, vp]),
+    "geoa3_mesh_edge_lengths": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_perp_jitter": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),
     "geoa3_smoothness": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "geoa3_sor_statistic": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),

@@ -86,7 +86,11 @@ class _SelfKnnTable:
 class AttackRunner:
     """Owns the device state of one batch of b attacks in flight and enqueues the loop."""
 
-    def __init__(self, net: PointNet, b: int, n: int, cfg, device, global_batch: Optional[int] = None):
+    def __init__(self, net: PointNet, b: int, n: int, cfg, device, global_batch: Optional[int] = None,
+                 ne: Optional[int] = None, geo_n: Optional[int] = None):
+        # ne, geo_n (a subclass whose variable is not the cloud itself, geoa3_amd/mesh_attack.py): the points of the cloud
+        # the objective is evaluated on, and of the clean cloud the geometry stages compare it with.  Default: derived
+        # from n as below, and n.
         # --uniform_loss_weight (geoA3_attack.py:168-174): w * U joins every row's constrain loss; U is ONE scalar for the
         # batch (Lib/loss_utils.py:151-189), so its gradient couples the rows -- a sharded batch would need an all-reduce
         self.w_uni = float(_cfg(cfg, "uniform_loss_weight", 0.0))
@@ -110,7 +114,7 @@ class AttackRunner:
         # logits = net(x); logits.backward(dlogits) -- still no host synchronisation.
         from .pointnet2 import PointNet2ClassificationSSG
         self.ssg = (isinstance(net, PointNet2ClassificationSSG) and not net.training and not net.use_normal and
-                    min(n, int(_cfg(cfg, "npoint", n))) >= PointNet2ClassificationSSG.MIN_POINTS)
+                    (min(n, int(_cfg(cfg, "npoint", n))) if ne is None else ne) >= PointNet2ClassificationSSG.MIN_POINTS)
         self.native = isinstance(net, PointNet) or self.ssg
         if self.native:
             self.packed = net.packed(device)
@@ -141,7 +145,8 @@ class AttackRunner:
         self.partial = bool(_cfg(cfg, "is_partial_var", False))
         self.kr = int(_cfg(cfg, "knn_range", 3))
         self.sub = bool(_cfg(cfg, "is_subsample_opt", False)) and n > self.npoint and not self.partial
-        self.ne = self.npoint if self.sub else n          # points the objective is evaluated on
+        self.ne = (self.npoint if self.sub else n) if ne is None else int(ne)   # points the objective is evaluated on
+        self.geo_n = n if geo_n is None else int(geo_n)   # points of the clean cloud of the geometry stages (geo_ori)
         self.eval_num = int(_cfg(cfg, "eval_num", 1))
         if self.sub and not 1 <= self.eval_num <= 64:
             raise ValueError("eval_num must be in 1..64")
@@ -166,7 +171,7 @@ class AttackRunner:
         self.late_join = (b <= 96) if lj is None else bool(lj)
         # the 1-NN tables through the pruned searches (geom_grid.hip / geom_filter.hip; same bits as the all-pairs kernel,
         # which stays the path for clouds of fewer than 32 points or when cfg.brute_force_nn1 is set)
-        self.grid_nn1 = min(n, self.ne) >= 32 and not _cfg(cfg, "brute_force_nn1", False)
+        self.grid_nn1 = min(self.geo_n, self.ne) >= 32 and not _cfg(cfg, "brute_force_nn1", False)
         # (tools: GEOA3_NN1_POLICY="brute_frac,filter" runs the loop's searches through geoa3_debug_grid_nn1_pair -- same
         # bits, another split between grid walk, in-kernel sweep and filter search: include/geoa3_hip_debug.h)
         pol = os.environ.get("GEOA3_NN1_POLICY")
@@ -203,8 +208,8 @@ class AttackRunner:
         t["ok"] = torch.zeros(b, **i32)
         t["loss_hist"] = z(self.iters, b)
         t["logits"], t["dlogits"] = z(b, self.classes), z(b, self.classes)
-        t["d_ao"], t["d_oa"] = z(b, ne), z(b, n)
-        t["i_ao"], t["i_oa"] = torch.zeros(b, ne, **i32), torch.zeros(b, n, **i32)
+        t["d_ao"], t["d_oa"] = z(b, ne), z(b, self.geo_n)
+        t["i_ao"], t["i_oa"] = torch.zeros(b, ne, **i32), torch.zeros(b, self.geo_n, **i32)
         if self.sub and _cfg(cfg, "is_pro_grad", False):   # the projections search with all n points
             t["proj_d"], t["proj_i"] = z(b, n), torch.zeros(b, n, **i32)
         else:
@@ -312,6 +317,8 @@ class AttackRunner:
                 self.packed.struct.flags = ab_flags()
         self.ori = pc_ori.to(self.dev, torch.float32).contiguous()
         self.nrm = normal_ori.to(self.dev, torch.float32).contiguous()
+        # the clean cloud of the geometry stages and its normals: the clean variable itself, unless a subclass says otherwise
+        self.geo_ori, self.geo_nrm = self._clean_geometry()
         self.gt = gt.to(self.dev, torch.int32).contiguous()
         self.target = target.to(self.dev, torch.int32).contiguous()
         t["scale_const"].fill_(float(cfg.initial_const))
@@ -325,18 +332,18 @@ class AttackRunner:
         self.nn1_seeded = False
         knn_ori_d = knn_ori = None
         if self.use_curv:  # _get_kappa_ori once per batch (geoA3_attack.py:216-217)
-            knn_ori_d, knn_ori = ops.knn_planar(self.ori, self.ori, self.k + 1)
-            self.kappa_ori = ops.kappa(self.ori, self.nrm, knn_ori)
+            knn_ori_d, knn_ori = ops.knn_planar(self.geo_ori, self.geo_ori, self.k + 1)
+            self.kappa_ori = ops.kappa(self.geo_ori, self.geo_nrm, knn_ori)
             self.curv_table.reset(None if self.sub else knn_ori)
         # the first prior of a term's own search: the clean cloud's neighbours (none for a sample: other points)
-        own_prior = lambda tb: None if self.sub else ops.knn_planar(self.ori, self.ori, tb.cols)[1]
+        own_prior = lambda tb: None if self.sub else ops.knn_planar(self.geo_ori, self.geo_ori, tb.cols)[1]
         if self.ks_table is not None:
             self.ks_table.reset(own_prior(self.ks_table))
         if self.w_disp != 0:   # displacement_loss reads the CLEAN cloud's neighbours (Lib/loss_utils.py:101): once per batch
             if self.disp_share:
                 self.disp_table = (knn_ori_d, knn_ori, self.k + 1)
             else:
-                ops.knn_planar(self.ori, self.ori, self.k_disp + 1, out=(t["disp_knn_d"], t["disp_knn"]))
+                ops.knn_planar(self.geo_ori, self.geo_ori, self.k_disp + 1, out=(t["disp_knn_d"], t["disp_knn"]))
                 self.disp_table = (t["disp_knn_d"], t["disp_knn"], self.k_disp + 1)
         if self.reg_table is not None:
             self.reg_table.reset(own_prior(self.reg_table))
@@ -350,6 +357,13 @@ class AttackRunner:
             iter_best_loss=self._p(t["iter_best_loss"]), iter_best_score=self._p(t["iter_best_score"]),
             prev_constrain=self._p(t["prev_constrain"]), label=self._p(t["label"]), cls_loss=self._p(t["cls_loss"]),
             loss_n=self._p(t["loss_n"]), loss_hist=self._p(t["loss_hist"]), last_label=self._p(t["last_label"]))
+
+    def _clean_geometry(self):
+        """-> (clean cloud [b,3,geo_n], its normals) of the geometry stages, called by setup() once self.ori / self.nrm stand"""
+        return self.ori, self.nrm
+
+    def _variable_terms(self, sg: int):
+        """Constraint terms on the optimised variable itself rather than on xe, folded last (a subclass; none here)"""
 
     # ------------------------------------------------------------------------------------
     def begin_search_step(self, init_offset: Optional[Tensor]):
@@ -516,6 +530,7 @@ class AttackRunner:
                 self._point_regularisers(xe, sg, curv)
             if self.w_uni != 0:
                 self._uniform(xe, sg)
+            self._variable_terms(sg)
         if self.geo_stream is not None:     # join: the bookkeeping needs the constrain loss, the update the gradient
             self.ev_geo.record(self.geo_stream)
             if not late:
@@ -542,7 +557,7 @@ class AttackRunner:
         ao = (t["d_ao"], t["i_ao"]) if self.need_nn else (None, None)
         oa = (t["d_oa"], t["i_oa"]) if self.both else (None, None)
         if self.need_nn:
-            head = (xe.data_ptr(), self.ori.data_ptr(), self.b, self.ne, self.n)
+            head = (xe.data_ptr(), self.geo_ori.data_ptr(), self.b, self.ne, self.geo_n)
             out = [self._p(x) for x in ao + oa]
             if self.grid_nn1:   # seeded with the tables of the previous iteration (in place)
                 pa, pr = (out[1], out[3]) if self.nn1_seeded else (None, None)
@@ -553,7 +568,7 @@ class AttackRunner:
             else:
                 check(lib.geoa3_nn1_pair(*head, *out, sg), "nn1_pair")
         curv = self.curv_table.search(xe, sg) if self.use_curv else None
-        ops.geo_loss_grad(xe, self.ori, normal_ori=self.nrm if self.use_curv else None, kappa_ori=self.kappa_ori,
+        ops.geo_loss_grad(xe, self.geo_ori, normal_ori=self.geo_nrm if self.use_curv else None, kappa_ori=self.kappa_ori,
                           d_ao=ao[0], i_ao=ao[1], d_oa=oa[0], i_oa=oa[1], knn_adv=curv[1] if curv else None,
                           k=self.k if self.use_curv else 0, dis_type=self.dis_type,
                           single_side=bool(cfg.is_cd_single_side), w_dis=float(cfg.dis_loss_weight),
@@ -576,7 +591,7 @@ class AttackRunner:
         t, lib, b, ne, ws = self.t, self.lib, self.b, self.ne, self.reg_ws.data_ptr()
         if self.w_disp != 0:   # on the CLEAN cloud's table (setup())
             clean = self.disp_table
-            head = (xe.data_ptr(), self.ori.data_ptr(), b, ne, self.k_disp, clean[0].data_ptr(), clean[1].data_ptr(), clean[2])
+            head = (xe.data_ptr(), self.geo_ori.data_ptr(), b, ne, self.k_disp, clean[0].data_ptr(), clean[1].data_ptr(), clean[2])
             check(lib.geoa3_displacement_loss(*head, t["disp_out"].data_ptr(), ws, sg), "displacement_loss")
             check(lib.geoa3_displacement_loss_grad(*head, None, t["disp_grad"].data_ptr(), ws, sg), "displacement_loss_grad")
         if self.w_rep != 0 or self.w_cn != 0:
@@ -591,9 +606,9 @@ class AttackRunner:
             # non-finite coordinate has no neighbours (index -1, which geoa3_kappa does not follow: its term is NaN, and
             # so is the row's mean).  The gradient kernel reads the table itself and refuses such a row whole.
             t["cn_knn"].copy_(reg[1][:, :, :self.k_cn + 1])
-            check(lib.geoa3_kappa(xe.data_ptr(), self.nrm.data_ptr(), t["cn_knn"].data_ptr(), None, b, ne, ne, self.k_cn,
+            check(lib.geoa3_kappa(xe.data_ptr(), self.geo_nrm.data_ptr(), t["cn_knn"].data_ptr(), None, b, ne, ne, self.k_cn,
                                   t["cn_out"].data_ptr(), sg), "kappa")
-            check(lib.geoa3_corr_normal_loss_grad(xe.data_ptr(), self.nrm.data_ptr(), b, ne, self.k_cn, *reg_ptrs, None,
+            check(lib.geoa3_corr_normal_loss_grad(xe.data_ptr(), self.geo_nrm.data_ptr(), b, ne, self.k_cn, *reg_ptrs, None,
                                                   t["cn_grad"].data_ptr(), ws, sg), "corr_normal_loss_grad")
         for name, w, _ in self.point_terms:
             self._fold(sg, ops.reg_fold_points, t[name + "_out"], t[name + "_grad"], w, term=t[name + "_loss"])

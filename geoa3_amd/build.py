@@ -51,6 +51,8 @@ for _f in ("pointnet2_sa.hip", "pointnet2_sa2.hip", "pointnet2_sa2b.hip", "geom_
 # mesh_sample.hip: its float32 point and float64 area / normal are held to the numpy restatement operation by operation
 # (tests/test_gpu_mesh_kernels.py: points bit for bit), so no multiply may fuse into an add
 FILE_FLAGS["mesh_sample.hip"] = ["-ffp-contract=off"] + _NOSLP
+# mesh_attack.hip: its point is held to mesh_sample.hip's bits, its pullback to a float32 loop's (tests/test_gpu_mesh_attack_kernels.py)
+FILE_FLAGS["mesh_attack.hip"] = ["-ffp-contract=off"] + _NOSLP
 
 
 def sources():

@@ -19,6 +19,8 @@ differentiates through it, a registered autograd formula.  `geoa3_amd.ops.knn_po
     geoa3::kappa_adv       _get_kappa_adv with autograd                               Lib/loss_utils.py:64-82
     geoa3::uniform_loss    uniform_loss (one scalar for the batch) with autograd      Lib/loss_utils.py:151-189
     geoa3::knn_smoothing_loss / repulsion_loss / displacement_loss / corresponding_normal_loss  with autograd  Lib/loss_utils.py:99-149
+    geoa3::mesh_surface_points / _grad   pytorch3d's sample_points_from_meshes at a fixed draw and its ordered pullback
+    geoa3::mesh_reg / _grad   pytorch3d's mesh_laplacian_smoothing(method="uniform") and mesh_edge_loss per mesh   main_attack.py:283-293
     geoa3::pointnet_forward / _backward   PointNet.forward (eval) and its input gradient   Model/PointNet.py:132-160
 """
 from __future__ import annotations
@@ -506,6 +508,107 @@ def _cnl_backward(ctx, g, _gi):
 
 
 corresponding_normal_loss.register_autograd(_cnl_backward, setup_context=_cnl_setup)
+
+
+# ------------------------------------------------------------------------------------------------ the mesh attack
+# pytorch3d's sample_points_from_meshes at a fixed draw, mesh_laplacian_smoothing(method="uniform") and mesh_edge_loss on
+# planar padded vertices [B,3,Vp] (geoa3_amd.mesh: surface_points, mesh_laplacian_smoothing, mesh_edge_loss)
+@custom_op("geoa3::mesh_surface_points", mutates_args=(), device_types="cuda")
+def mesh_surface_points(verts: Tensor, nv: Tensor, faces: Tensor, face_off: Tensor, face_idx: Tensor, u: Tensor,
+                        lists: Optional[Tensor]) -> Tensor:
+    """verts [B,3,Vp], nv i32 [B], faces i32 [sumF,3], face_off i64 [B+1], face_idx i32 [B,S], u [B,S,3] -> pts [B,3,S].
+    lists: mesh_point_lists of the draw for the backward (None: it sorts the draw itself)."""
+    from . import mesh
+    return mesh.mesh_points_forward(verts, nv, faces, face_off, face_idx, u)
+
+
+@mesh_surface_points.register_fake
+def _(verts, nv, faces, face_off, face_idx, u, lists):
+    return verts.new_empty(verts.shape[0], 3, face_idx.shape[1], dtype=_f32)
+
+
+@custom_op("geoa3::mesh_surface_points_grad", mutates_args=(), device_types="cuda")
+def mesh_surface_points_grad(g: Tensor, nv: Tensor, faces: Tensor, face_off: Tensor, face_idx: Tensor, u: Tensor,
+                             lists: Optional[Tensor], vp: int) -> Tensor:
+    """The pullback of geoa3::mesh_surface_points: g [B,3,S] -> d verts [B,3,vp], every vertex's terms in ascending
+    (sample, corner) order."""
+    from . import mesh
+    if lists is None:
+        lists = mesh.mesh_point_lists(nv, faces, face_off, face_idx, vp)
+    return mesh.mesh_points_backward(g, u, lists, vp)
+
+
+@mesh_surface_points_grad.register_fake
+def _(g, nv, faces, face_off, face_idx, u, lists, vp):
+    return g.new_empty(g.shape[0], 3, vp, dtype=_f32)
+
+
+mesh_surface_points_grad.register_autograd(_no_second_derivative("mesh_surface_points_grad"))
+
+
+def _mesh_points_setup(ctx, inputs, output):
+    verts, nv, faces, face_off, face_idx, u, lists = inputs
+    ctx.save_for_backward(nv, faces, face_off, face_idx, u)
+    ctx.lists, ctx.vp, ctx.dtype = lists, verts.shape[2], verts.dtype
+
+
+def _mesh_points_backward(ctx, g):
+    nv, faces, face_off, face_idx, u = ctx.saved_tensors
+    gv = torch.ops.geoa3.mesh_surface_points_grad(g, nv, faces, face_off, face_idx, u, ctx.lists, ctx.vp)
+    return gv.to(ctx.dtype), None, None, None, None, None, None
+
+
+mesh_surface_points.register_autograd(_mesh_points_backward, setup_context=_mesh_points_setup)
+
+
+@custom_op("geoa3::mesh_reg", mutates_args=(), device_types="cuda")
+def mesh_reg(verts: Tensor, nv: Tensor, row_off: Tensor, col: Tensor, ne: Tensor, target: Optional[Tensor],
+             target_scalar: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """verts [B,3,Vp] and the CSR of a MeshTopology -> (Lap_b [B], Edge_b [B], unit [B,4,Vp] = (u_i, |delta_i|) for the
+    gradient).  target: one length per CSR entry, or None for target_scalar."""
+    from . import mesh
+    return mesh.mesh_reg_forward(verts, nv, row_off, col, ne, target, target_scalar)
+
+
+@mesh_reg.register_fake
+def _(verts, nv, row_off, col, ne, target, target_scalar):
+    b = verts.shape[0]
+    return (verts.new_empty(b, dtype=_f32), verts.new_empty(b, dtype=_f32), verts.new_empty(b, 4, verts.shape[2], dtype=_f32))
+
+
+@custom_op("geoa3::mesh_reg_grad", mutates_args=(), device_types="cuda")
+def mesh_reg_grad(verts: Tensor, nv: Tensor, row_off: Tensor, col: Tensor, ne: Tensor, target: Optional[Tensor],
+                  target_scalar: float, unit: Tensor, g_lap: Optional[Tensor], g_edge: Optional[Tensor]) -> Tensor:
+    """d (g_lap . Lap + g_edge . Edge) / d verts [B,3,Vp] in one gather over the CSR; a term whose g is None is skipped."""
+    from . import mesh
+    return mesh.mesh_reg_backward(verts, nv, row_off, col, ne, target, target_scalar, unit, g_lap, g_edge,
+                                  w_lap=0.0 if g_lap is None else 1.0, w_edge=0.0 if g_edge is None else 1.0)
+
+
+@mesh_reg_grad.register_fake
+def _(verts, nv, row_off, col, ne, target, target_scalar, unit, g_lap, g_edge):
+    return verts.new_empty(verts.shape, dtype=_f32)
+
+
+mesh_reg_grad.register_autograd(_no_second_derivative("mesh_reg_grad"))
+
+
+def _mesh_reg_setup(ctx, inputs, output):
+    verts, nv, row_off, col, ne, target, target_scalar = inputs
+    ctx.save_for_backward(verts, nv, row_off, col, ne, output[2])
+    ctx.target, ctx.target_scalar = target, target_scalar
+    ctx.set_materialize_grads(False)   # a term nobody reads arrives as None and is skipped, not multiplied by 0
+
+
+def _mesh_reg_backward(ctx, g_lap, g_edge, _g_unit):
+    verts, nv, row_off, col, ne, unit = ctx.saved_tensors
+    if g_lap is None and g_edge is None:
+        return (None,) * 7
+    gv = torch.ops.geoa3.mesh_reg_grad(verts, nv, row_off, col, ne, ctx.target, ctx.target_scalar, unit, g_lap, g_edge)
+    return gv.to(verts.dtype), None, None, None, None, None, None
+
+
+mesh_reg.register_autograd(_mesh_reg_backward, setup_context=_mesh_reg_setup)
 
 # ------------------------------------------------------------------------------------------------ the victim
 import weakref

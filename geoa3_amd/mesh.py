@@ -7,7 +7,16 @@ dense clouds with exact face normals that the re-sampling and the attack consume
     (pts, nrm), (dense_pts, dense_nrm) = mesh_clouds(packed, 1024, 10000)
 
 The random draws stay the caller's (`u`, `first`), drawn with torch where they are not given.  No CPU path for the
-sampler; the readers and writers are plain numpy."""
+sampler; the readers and writers are plain numpy.
+
+For the mesh attack (geoa3_amd/mesh_attack.py; mesh_attack.hip) the vertices are the variable: to_planar / from_planar,
+MeshTopology (edges and CSR, built on the host), and three differentiable operators on planar padded vertices [B,3,Vp] --
+surface_points (the points of a FIXED draw at the current vertices), mesh_laplacian_smoothing and mesh_edge_loss
+(pytorch3d's, per mesh).
+
+    x, nv = to_planar(packed); topo = MeshTopology.from_packed(packed)
+    pts0, nrm0, face_idx, _ = sample_surface(packed, S, u=u)
+    loss = f(surface_points(x, nv, packed, face_idx, u)) + mesh_laplacian_smoothing(x, nv, topo).sum()"""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional, Sequence, Tuple
@@ -272,3 +281,246 @@ def mesh_clouds(packed, npoint: int, dense_npoints: int, surface_samples: int = 
     small = U.farthest_points_normalized(pts, nrm, int(npoint), firsts[0])
     dense = U.farthest_points_normalized(pts, nrm, int(dense_npoints), firsts[1]) if dense_npoints > 0 else None
     return (small, dense, bad) if return_bad_faces else (small, dense)
+
+
+# ------------------------------------------------------------------ the mesh attack: vertices as the optimised variable
+# (main_attack.py:27-28, 283-293: --attack GeoA3_mesh, which the reference parses and never published.)  The vertices are
+# held as the attack loop holds every cloud, planar and padded: verts f32 [B,3,Vp], nv i32 [B]; the faces stay packed.
+def to_planar(packed, vp: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """PackedMeshes -> (verts f32 [B,3,Vp], nv i32 [B]); Vp = the largest vertex count (at least 1) unless given.  Padding
+    columns are 0.  Reads vert_off on the host."""
+    verts, _, vert_off, _ = packed
+    vo = vert_off.cpu().tolist()
+    nvs = [vo[i + 1] - vo[i] for i in range(len(vo) - 1)]
+    width = max(1, max(nvs)) if vp is None else int(vp)
+    if width < max(nvs):
+        raise ValueError("vp = %d is smaller than the largest mesh (%d vertices)" % (width, max(nvs)))
+    out = verts.new_zeros(len(nvs), 3, width, dtype=torch.float32)
+    for b, n in enumerate(nvs):
+        if n:
+            out[b, :, :n] = verts[vo[b]:vo[b + 1]].t()
+    return out, torch.tensor(nvs, dtype=torch.int32, device=verts.device)
+
+
+def from_planar(verts: Tensor, nv: Tensor, packed) -> PackedMeshes:
+    """The inverse of to_planar: the packed batch with its vertices replaced by verts [B,3,Vp] cut to nv (same faces)."""
+    counts = nv.cpu().tolist()
+    rows = [verts[b, :, :n].t() for b, n in enumerate(counts)]
+    out = PackedMeshes(torch.cat(rows).contiguous().float(), packed[1], packed[2], packed[3])
+    out.max_faces = getattr(packed, "max_faces", -1)
+    return out
+
+
+class MeshTopology:
+    """The fixed topology of a batch, built once on the host from the faces:
+        edges    i32 [sumE,2]   the unique undirected edges {i,j}, i < j, local indices, sorted by (i, j); edge_off i64 [B+1]
+        row_off  i32 [B Vp + 1] one CSR over the B Vp rows of the padded batch (row b Vp + v; a padding row is empty)
+        col      i32 [nnz]      N(v): the neighbours of the row's vertex, local, ASCENDING -- the order every sum runs in
+        ne, nv   i32 [B]        E_b and V_b
+    A face with an index outside [0,V_b) contributes nothing (the sampler's rule), a face that repeats an index only its
+    i != j pairs."""
+
+    def __init__(self, edges, edge_off, row_off, col, ne, nv, vp):
+        self.edges, self.edge_off, self.row_off, self.col, self.ne, self.nv, self.vp = edges, edge_off, row_off, col, ne, nv, vp
+
+    @property
+    def batch(self) -> int:
+        return self.nv.numel()
+
+    @property
+    def nnz(self) -> int:
+        return self.col.numel()
+
+    @classmethod
+    def from_packed(cls, packed, vp: Optional[int] = None) -> "MeshTopology":
+        _, faces, vert_off, face_off = packed
+        dev = faces.device
+        f = faces.cpu().numpy().astype(np.int64).reshape(-1, 3)
+        vo, fo = vert_off.cpu().numpy(), face_off.cpu().numpy()
+        nvs = np.diff(vo).astype(np.int64)
+        b = len(nvs)
+        width = max(1, int(nvs.max())) if vp is None else int(vp)
+        if width < nvs.max():
+            raise ValueError("vp = %d is smaller than the largest mesh (%d vertices)" % (width, nvs.max()))
+        if b * (width + 1) > 2 ** 31 - 257:
+            raise _lib.Geoa3Error("the padded batch has %d x %d rows, more than the kernels index" % (b, width))
+        edges, cols, degs = [], [], np.zeros((b, width), np.int64)
+        for i in range(b):
+            v = int(nvs[i])
+            fb = f[fo[i]:fo[i + 1]]
+            fb = fb[((fb >= 0) & (fb < v)).all(1)]
+            pairs = np.concatenate([fb[:, [0, 1]], fb[:, [1, 2]], fb[:, [2, 0]]])
+            pairs = pairs[pairs[:, 0] != pairs[:, 1]]
+            key = np.unique(pairs.min(1) * max(v, 1) + pairs.max(1))       # sorted: by the smaller end, then the larger
+            e = np.stack([key // max(v, 1), key % max(v, 1)], 1)
+            both = np.concatenate([e, e[:, ::-1]])
+            both = both[np.lexsort((both[:, 1], both[:, 0]))]              # rows ascending, neighbours ascending inside
+            degs[i] = np.bincount(both[:, 0], minlength=width)
+            edges.append(e)
+            cols.append(both[:, 1])
+        ne = np.array([len(e) for e in edges], np.int64)
+        if 2 * ne.sum() >= 2 ** 31:
+            raise _lib.Geoa3Error("the batch has %d edges, more than the CSR indexes" % ne.sum())
+        row_off = np.concatenate([[0], np.cumsum(degs.reshape(-1))])
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(dev)
+        return cls(t(np.concatenate(edges).reshape(-1, 2), np.int32), t(np.concatenate([[0], np.cumsum(ne)]), np.int64),
+                   t(row_off, np.int32), t(np.concatenate(cols), np.int32), t(ne, np.int32), t(nvs, np.int32), width)
+
+    def _check(self, verts: Tensor):
+        if not verts.is_cuda:
+            raise _lib.Geoa3Error("geoa3_amd.mesh has no CPU path: the vertices must be on the GPU")
+        if verts.dim() != 3 or tuple(verts.shape) != (self.batch, 3, self.vp):
+            raise ValueError("verts must be [B,3,Vp] = %r, not %r" % ((self.batch, 3, self.vp), tuple(verts.shape)))
+
+    def edge_lengths(self, verts: Tensor) -> Tensor:
+        """l_ij of every CSR entry, f32 [nnz] (geoa3_mesh_edge_lengths): as target_length of mesh_edge_loss it makes the
+        term and its gradient exactly 0 at these vertices."""
+        self._check(verts)
+        v = verts.detach().contiguous().float()
+        out = torch.empty(self.nnz, device=v.device, dtype=torch.float32)
+        check(_lib.load().geoa3_mesh_edge_lengths(v.data_ptr(), self.nv.data_ptr(), self.row_off.data_ptr(), _ptr(self.col),
+                                                  self.batch, self.vp, self.nnz, _ptr(out), _stream()), "geoa3_mesh_edge_lengths")
+        return out
+
+
+def _faces_of(packed_faces) -> Tuple[Tensor, Tensor]:
+    """(faces i32 [sumF,3], face_off i64 [B+1]) of a PackedMeshes, a 4-tuple or the pair itself"""
+    if len(packed_faces) == 4:
+        return packed_faces[1], packed_faces[3]
+    faces, face_off = packed_faces
+    return faces, face_off
+
+
+def _check_draw(verts, nv, faces, face_off, face_idx, u):
+    b, vp = verts.shape[0], verts.shape[2]
+    if not verts.is_cuda:
+        raise _lib.Geoa3Error("geoa3_amd.mesh has no CPU path: the vertices must be on the GPU")
+    if verts.dim() != 3 or verts.shape[1] != 3 or nv.numel() != b or face_off.numel() != b + 1:
+        raise ValueError("verts must be [B,3,Vp] with nv [B] and face_off [B+1]")
+    if face_idx.dim() != 2 or face_idx.shape[0] != b or tuple(u.shape) != (b, face_idx.shape[1], 3):
+        raise ValueError("face_idx must be [B,S] and u [B,S,3]")
+    if (nv.dtype, faces.dtype, face_off.dtype, face_idx.dtype) != (torch.int32, torch.int32, torch.int64, torch.int32):
+        raise TypeError("nv, faces and face_idx are int32, face_off int64")
+    return b, vp, int(face_idx.shape[1])
+
+
+def mesh_points_forward(verts, nv, faces, face_off, face_idx, u) -> Tensor:
+    """geoa3_mesh_points: pts f32 [B,3,S] of the draw (face_idx, u) at verts [B,3,Vp].  No autograd (surface_points)."""
+    b, vp, s = _check_draw(verts, nv, faces, face_off, face_idx, u)
+    v, uu = verts.detach().contiguous().float(), u.detach().contiguous().float()
+    pts = torch.empty(b, 3, s, device=v.device, dtype=torch.float32)
+    check(_lib.load().geoa3_mesh_points(v.data_ptr(), nv.data_ptr(), _ptr(faces), face_off.data_ptr(),
+                                        face_idx.contiguous().data_ptr(), uu.data_ptr(), b, vp, s, faces.shape[0],
+                                        pts.data_ptr(), _stream()), "geoa3_mesh_points")
+    return pts
+
+
+def mesh_corner_index(nv, faces, face_off, face_idx, vp: int) -> Tensor:
+    """geoa3_mesh_corner_index: i32 [B,3S], entry 3 s + k = the vertex of corner k of sample s (-1: no face)."""
+    b, s = face_idx.shape
+    corner = torch.empty(b, 3 * s, device=face_idx.device, dtype=torch.int32)
+    check(_lib.load().geoa3_mesh_corner_index(nv.data_ptr(), _ptr(faces), face_off.data_ptr(), face_idx.contiguous().data_ptr(),
+                                              b, int(vp), s, faces.shape[0], corner.data_ptr(), _stream()),
+          "geoa3_mesh_corner_index")
+    return corner
+
+
+def mesh_point_lists(nv, faces, face_off, face_idx, vp: int) -> Tensor:
+    """The destination lists of a draw's pullback (every vertex's (sample, corner) entries in ascending order), built ONCE
+    per draw: an opaque int32 tensor for mesh_points_backward."""
+    b, s = face_idx.shape
+    lib = _lib.load()
+    nbytes = lib.geoa3_mesh_points_scratch_bytes(b, int(vp), s)
+    if nbytes < 0:
+        check(int(nbytes), "geoa3_mesh_points_scratch_bytes")
+    corner = mesh_corner_index(nv, faces, face_off, face_idx, vp)
+    lists = torch.empty(nbytes // 4, device=face_idx.device, dtype=torch.int32)
+    check(lib.geoa3_mesh_points_lists(corner.data_ptr(), b, int(vp), s, lists.data_ptr(), _stream()), "geoa3_mesh_points_lists")
+    return lists
+
+
+def mesh_points_backward(g_pts: Tensor, u: Tensor, lists: Tensor, vp: int, out: Optional[Tensor] = None) -> Tensor:
+    """geoa3_mesh_points_grad: g_pts [B,3,S] -> g_verts [B,3,Vp], every vertex's float32 products added in ascending
+    (sample, corner) order."""
+    b, _, s = g_pts.shape
+    g, uu = g_pts.detach().contiguous().float(), u.detach().contiguous().float()
+    if out is None:
+        out = torch.empty(b, 3, int(vp), device=g.device, dtype=torch.float32)
+    check(_lib.load().geoa3_mesh_points_grad(g.data_ptr(), uu.data_ptr(), lists.data_ptr(), b, int(vp), s, out.data_ptr(),
+                                             _stream()), "geoa3_mesh_points_grad")
+    return out
+
+
+def mesh_reg_forward(verts, nv, row_off, col, ne, target: Optional[Tensor], target_scalar: float):
+    """geoa3_mesh_reg -> (lap [B], edge [B], unit [B,4,Vp])"""
+    b, _, vp = verts.shape
+    if not verts.is_cuda:
+        raise _lib.Geoa3Error("geoa3_amd.mesh has no CPU path: the vertices must be on the GPU")
+    if target is not None and target.numel() != col.numel():
+        raise ValueError("a per-edge target_length holds one value per CSR entry (%d), got %d" % (col.numel(), target.numel()))
+    v = verts.detach().contiguous().float()
+    lap, edge = (torch.empty(b, device=v.device, dtype=torch.float32) for _ in range(2))
+    unit = torch.empty(b, 4, vp, device=v.device, dtype=torch.float32)
+    tg = None if target is None else target.detach().contiguous().float()
+    check(_lib.load().geoa3_mesh_reg(v.data_ptr(), nv.data_ptr(), row_off.data_ptr(), _ptr(col), ne.data_ptr(),
+                                     None if tg is None else _ptr(tg), float(target_scalar), b, vp, col.numel(), 0.0, 0.0,
+                                     unit.data_ptr(), lap.data_ptr(), edge.data_ptr(), None, 0, _stream()), "geoa3_mesh_reg")
+    return lap, edge, unit
+
+
+def mesh_reg_backward(verts, nv, row_off, col, ne, target: Optional[Tensor], target_scalar: float, unit: Tensor,
+                      g_lap: Optional[Tensor], g_edge: Optional[Tensor], w_lap: float = 1.0, w_edge: float = 1.0,
+                      out: Optional[Tensor] = None, add: bool = False) -> Tensor:
+    """geoa3_mesh_reg_grad -> g_verts [B,3,Vp] = (add ? out : 0) + w_lap g_lap[b] dLap_b + w_edge g_edge[b] dEdge_b; a
+    weight of 0 skips its term (g_lap / g_edge None: ones)."""
+    b, _, vp = verts.shape
+    v = verts.detach().contiguous().float()
+    if out is None:
+        if add:
+            raise ValueError("add needs the tensor to add to")
+        out = torch.empty(b, 3, vp, device=v.device, dtype=torch.float32)
+    tg = None if target is None else target.detach().contiguous().float()
+    gl = None if g_lap is None else g_lap.detach().contiguous().float()
+    ge = None if g_edge is None else g_edge.detach().contiguous().float()
+    check(_lib.load().geoa3_mesh_reg_grad(v.data_ptr(), nv.data_ptr(), row_off.data_ptr(), _ptr(col), ne.data_ptr(),
+                                          None if tg is None else _ptr(tg), float(target_scalar), unit.data_ptr(),
+                                          None if gl is None else gl.data_ptr(), None if ge is None else ge.data_ptr(),
+                                          float(w_lap), float(w_edge), b, vp, col.numel(), out.data_ptr(), int(add), _stream()),
+          "geoa3_mesh_reg_grad")
+    return out
+
+
+def surface_points(verts: Tensor, nv: Tensor, packed_faces, face_idx: Tensor, u: Tensor, lists: Optional[Tensor] = None) -> Tensor:
+    """pytorch3d.ops.sample_points_from_meshes at a FIXED draw: the points [B,3,S] of the draw (face_idx, u) --
+    sample_surface's outputs and inputs -- at the current vertices [B,3,Vp]; at the vertices the draw was made on, its
+    points bit for bit.  Differentiable in verts (geoa3::mesh_surface_points): the backward is the ordered pullback;
+    lists = mesh_point_lists(...) of the draw spares it the sort."""
+    from . import library  # noqa: F401  (registers the geoa3:: operators)
+    faces, face_off = _faces_of(packed_faces)
+    return torch.ops.geoa3.mesh_surface_points(verts, nv, faces, face_off, face_idx, u, lists)
+
+
+def _reduce(x: Tensor, reduction: Optional[str]) -> Tensor:
+    if reduction is None:
+        return x
+    if reduction != "mean":
+        raise ValueError("reduction is None (the per-mesh terms [B]) or 'mean' (pytorch3d's batch value)")
+    return x.mean()
+
+
+def mesh_laplacian_smoothing(verts: Tensor, nv: Tensor, topo: MeshTopology, reduction: Optional[str] = None) -> Tensor:
+    """pytorch3d.loss.mesh_laplacian_smoothing(method="uniform") per mesh: Lap_b = (1/V_b) sum_i |mean_{j in N(i)} v_j - v_i|
+    -> [B]; reduction="mean": pytorch3d's batch value.  Differentiable in verts, d|x| at 0 taken as 0."""
+    from . import library  # noqa: F401
+    topo._check(verts)
+    return _reduce(torch.ops.geoa3.mesh_reg(verts, nv, topo.row_off, topo.col, topo.ne, None, 0.0)[0], reduction)
+
+
+def mesh_edge_loss(verts: Tensor, nv: Tensor, topo: MeshTopology, target_length=0.0, reduction: Optional[str] = None) -> Tensor:
+    """pytorch3d.loss.mesh_edge_loss per mesh: Edge_b = (1/E_b) sum_{edges} (l_ij - t_ij)^2 -> [B]; target_length a number
+    or a tensor with one value per CSR entry (topo.edge_lengths(clean_verts): the clean mesh's own lengths)."""
+    from . import library  # noqa: F401
+    topo._check(verts)
+    per_edge = target_length if isinstance(target_length, torch.Tensor) else None
+    scalar = 0.0 if per_edge is not None else float(target_length)
+    return _reduce(torch.ops.geoa3.mesh_reg(verts, nv, topo.row_off, topo.col, topo.ne, per_edge, scalar)[1], reduction)

@@ -694,6 +694,59 @@ int geoa3_mesh_sample(const float* verts, const int32_t* faces, const int64_t* v
                       int64_t max_faces, float* pts, float* normals, int32_t* face_idx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh attack (main_attack.py:27-28, 283-293: --attack GeoA3_mesh, which the reference parses and never published; its
+ * two weights name pytorch3d's mesh_laplacian_smoothing and mesh_edge_loss).  The vertices are held as the attack loop
+ * holds every cloud: verts f32 [B,3,Vp] planar and padded, nv i32 [B] (V_b = nv[b] <= Vp; columns >= V_b are padding:
+ * never read, their gradient written as 0).  Faces as above: faces i32 [total_faces,3] local, face_off i64 [B+1].
+ * Topology: one CSR over the B Vp rows of the batch (row b Vp + v; padding rows empty): row_off i32 [B Vp + 1], col i32
+ * [nnz] = the neighbours N(i) of the row's vertex, local and ASCENDING (every sum runs in that order), ne i32 [B] = the
+ * number of undirected edges E_b.  Every device-side size is clamped to what the host states; an index outside its range
+ * is not followed.  Limits: B <= 65535, B (Vp + 1) and 3 S below 2^31 - 256, total_faces < 2^31 (GEOA3_ENOSUPPORT,
+ * nothing launched).  No float atomics: repeated calls are bit identical.  A NaN / inf vertex makes its own mesh's terms
+ * and the points on its faces NaN and moves nothing else.
+ * ------------------------------------------------------------------------------------------ */
+/* pytorch3d.ops.sample_points_from_meshes at a FIXED draw (face_idx i32 [B,S], u f32 [B,S,3]: what geoa3_mesh_sample
+ * returned and was given): pts f32 [B,3,S], p = (r1 a + r2 b) + r3 c with the weights of gen_data_mat.py:88-119 as
+ * geoa3_mesh_sample forms them, float32, no contraction -- at the vertices the draw was made on, geoa3_mesh_sample's point
+ * bit for bit.  face_idx outside [0,F_b) (-1: the sampler's "no face"), or a corner outside [0,V_b): a NaN point. */
+int geoa3_mesh_points(const float* verts, const int32_t* nv, const int32_t* faces, const int64_t* face_off,
+                      const int32_t* face_idx, const float* u, int B, int Vp, int S, int64_t total_faces, float* pts,
+                      void* stream);
+/* The pullback of geoa3_mesh_points (the backward of pytorch3d.ops.sample_points_from_meshes w.r.t. the vertices), three steps:
+ * corner i32 [B,3S]: entry 3 s + k = the vertex of corner k of sample s, -1 for a sample without a point;
+ * geoa3_mesh_points_lists sorts the entries by vertex into `scratch` (geoa3_mesh_points_scratch_bytes(B, Vp, S) bytes),
+ * ONCE per draw; geoa3_mesh_points_grad: g_verts [B,3,Vp] = for every vertex the sum of w_k(s) g_pts[b,:,s] over its
+ * entries in ascending (s, k), float32 products added sequentially from +0.0 (an empty list, the padding: +0.0). */
+int geoa3_mesh_corner_index(const int32_t* nv, const int32_t* faces, const int64_t* face_off, const int32_t* face_idx,
+                            int B, int Vp, int S, int64_t total_faces, int32_t* corner, void* stream);
+int64_t geoa3_mesh_points_scratch_bytes(int B, int Vp, int S);
+int geoa3_mesh_points_lists(const int32_t* corner, int B, int Vp, int S, void* scratch, void* stream);
+int geoa3_mesh_points_grad(const float* g_pts, const float* u, const void* scratch, int B, int Vp, int S,
+                           float* g_verts, void* stream);
+/* pytorch3d.loss.mesh_laplacian_smoothing(method="uniform") and pytorch3d.loss.mesh_edge_loss, per mesh, one pass:
+ *   delta_i = (sum_{j in N(i)} v_j) / deg_i - v_i (0 when deg_i = 0),  lap[b] = (1/V_b) sum_i |delta_i|  (0 when V_b = 0);
+ *   edge[b] = (1/E_b) sum_{i<j} (l_ij - t_ij)^2  (0 when E_b = 0),  l_ij = |v_i - v_j| formed in double and rounded to
+ *   float32 once, t_ij = target[q] of the CSR entry (target f32 [nnz]) or target_scalar when target is NULL.
+ * unit f32 [B,4,Vp] <- (delta_i / |delta_i|, taken as 0 when |delta_i| = 0; |delta_i|): what geoa3_mesh_reg_grad reads.
+ * Per-vertex terms in double, per-mesh sums reduced in double in a fixed order, rounded to float32 once.
+ * constrain [B] (optional) = ((constrain_add ? constrain : 0) + w_lap lap) + w_edge edge; a term whose weight is 0 is left out. */
+int geoa3_mesh_reg(const float* verts, const int32_t* nv, const int32_t* row_off, const int32_t* col, const int32_t* ne,
+                   const float* target, float target_scalar, int B, int Vp, int nnz, float w_lap, float w_edge,
+                   float* unit, float* lap, float* edge, float* constrain, int constrain_add, void* stream);
+/* The gradients of pytorch3d.loss.mesh_laplacian_smoothing / mesh_edge_loss, one gather over N(i) (the adjacency is symmetric):
+ *   g = w_lap g_lap[b] / V_b (-u_i [deg_i > 0] + sum_j u_j / deg_j) + w_edge g_edge[b] 2 / E_b sum_j (l_ij - t_ij)(v_i - v_j) / l_ij
+ * (summand 0 when l_ij = 0; g_lap, g_edge f32 [B], NULL means ones; a term whose weight is 0 is skipped, not multiplied);
+ * g_verts [B,3,Vp] = add ? g_verts + g : g, g rounded to float32 once; padding columns get g = 0. */
+int geoa3_mesh_reg_grad(const float* verts, const int32_t* nv, const int32_t* row_off, const int32_t* col,
+                        const int32_t* ne, const float* target, float target_scalar, const float* unit, const float* g_lap,
+                        const float* g_edge, float w_lap, float w_edge, int B, int Vp, int nnz, float* g_verts, int add,
+                        void* stream);
+/* len f32 [nnz] = l_ij of every CSR entry as geoa3_mesh_reg forms it: the target_length of pytorch3d.loss.mesh_edge_loss
+ * that makes the term and its gradient exactly 0 at the vertices it was taken on. */
+int geoa3_mesh_edge_lengths(const float* verts, const int32_t* nv, const int32_t* row_off, const int32_t* col, int B,
+                            int Vp, int nnz, float* len, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Uniformity term (Lib/loss_utils.py:151-189, uniform_loss; Attacker/geoA3_attack.py:168-174, --uniform_loss_weight).
  * ------------------------------------------------------------------------------------------ */
 /* loss [1] = U, ONE scalar for the batch: for every p of percentages[num_percentages] (p <- 4p, nsample = int(N p),

@@ -5,6 +5,9 @@ harness, :317-384 for the 44 flags), driving geoa3_amd.attack instead of Attacke
 
     python main_attack.py --attack GeoA3 --attack_label Untarget -b 250 [...]
 
+`--attack GeoA3_mesh` (the reference: "Not uploaded yet.") attacks the vertices of triangle meshes read from `--mesh_dir`
+(or `--synthetic` icospheres) and writes Mesh/<name>.obj and Mat/<name>.mat with `vert` / `faces` (main_mesh).
+
 Extensions (not in the reference): `--synthetic` writes a seeded synthetic `.mat` / uses calibrated random-init
 weights when the data file / checkpoint do not exist (neither ships with the reference repository);
 under `torchrun` (WORLD_SIZE > 1) every batch is sharded by instance over the ranks and rank 0 writes the files.
@@ -128,6 +131,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--quiet", action="store_true", default=False)
     p.add_argument("--synthetic_npoint", type=int, default=0,
                    help="points per synthetic cloud when --synthetic writes the data file (default: --npoint)")
+    p.add_argument("--mesh_dir", default=None, type=str,
+                   help="--attack GeoA3_mesh: triangle meshes ROOT/<class>/<split>/*.off|*.obj (the layout of "
+                        "Provider/gen_data_mat.py --mesh_dir), each centred and scaled to unit radius")
+    p.add_argument("--mesh_split", default="test", type=str)
+    p.add_argument("--shape_names_file", default=None, type=str,
+                   help="--mesh_dir: one class name per line, the line number is the label")
     p.add_argument("--synthetic_kind", default="ellipsoid", choices=["ellipsoid", "cad"],
                    help="what --synthetic writes: one ellipsoid per instance, or CAD-like clouds (boxes, tables on thin "
                         "legs, clusters of very different density, rods, exact duplicates)")
@@ -268,15 +277,132 @@ class CountLossIter:
         plt.close(fig)
 
 
+def load_victim(cfg, device, say):
+    """The victim of --arch in eval mode on `device`, from Pretrained/<arch>/<npoint>/model_best.pth.tar or, under
+    --synthetic, seeded stand-in weights.  -> (net, the checkpoint's path)"""
+    from geoa3_amd.data import synthetic_state_dict
+    say("=>Loading model")
+    model_path = os.path.join("Pretrained", cfg.arch, str(cfg.npoint), "model_best.pth.tar")
+    net = make_victim(cfg)
+    if os.path.isfile(model_path):
+        load_checkpoint(net, cfg, model_path)
+        say("==>Successfully load pretrained-model from {}".format(model_path))
+    elif cfg.synthetic and cfg.arch == "DGCNN":
+        say("==>No checkpoint at {}: the module's own seeded init (--synthetic)".format(model_path))
+    elif cfg.synthetic and cfg.arch == "PointNetPP":
+        with torch.no_grad():   # default-initialised modules (seeded above) with non-trivial BatchNorm statistics
+            for mod in net.modules():
+                if isinstance(mod, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
+                    mod.running_mean.normal_(0, 0.1)
+                    mod.running_var.uniform_(0.5, 1.5)
+        say("==>No checkpoint at {}: seeded random-init weights (--synthetic)".format(model_path))
+    elif cfg.synthetic:
+        net.load_state_dict(synthetic_state_dict(cfg.classes, seed=0, device=device))
+        say("==>No checkpoint at {}: calibrated random-init weights (--synthetic)".format(model_path))
+    else:
+        raise FileNotFoundError(model_path)
+    return net.to(device).eval(), model_path
+
+
+def load_meshes(cfg):
+    """The inputs of --attack GeoA3_mesh -> [(name, verts f32 [V,3], faces i32 [F,3], label or None)], every mesh centred
+    and scaled to unit radius.  --mesh_dir ROOT with --shape_names_file: ROOT/<class>/<split>/*.off|*.obj in the order of
+    the names file, the label its line number (the walker and rule of Provider/gen_data_mat.py); else --synthetic:
+    --batch_size seeded subdivided icosahedra, stretched per instance, whose label is the victim's own prediction."""
+    from geoa3_amd import mesh
+    from geoa3_amd.mesh_attack import normalize_mesh, synthetic_meshes
+    if cfg.mesh_dir is not None:
+        import importlib.util
+        spec = importlib.util.spec_from_file_location(
+            "gen_data_mat", os.path.join(os.path.dirname(os.path.abspath(__file__)), "Provider", "gen_data_mat.py"))
+        gdm = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(gdm)
+        if not cfg.shape_names_file:
+            raise ValueError("--mesh_dir needs --shape_names_file (one class name per line, the line number is the label)")
+        out = []
+        for label, cls in enumerate(gdm.read_shape_names(cfg.shape_names_file)):
+            folder, files = gdm.mesh_files(cfg.mesh_dir, cls, cfg.mesh_split)
+            for f in files:
+                v, faces = mesh.READERS[os.path.splitext(f)[1].lower()](os.path.join(folder, f))
+                out.append((os.path.splitext(f)[0], normalize_mesh(v), faces, label))
+        if not out:
+            raise FileNotFoundError("no *.off / *.obj under %s/<class>/%s" % (cfg.mesh_dir, cfg.mesh_split))
+        return out
+    if not cfg.synthetic:
+        raise ValueError("--attack GeoA3_mesh needs --mesh_dir ROOT (with --shape_names_file) or --synthetic")
+    return [("ico%d" % i, v, f, None) for i, (v, f) in enumerate(synthetic_meshes(cfg.batch_size, seed=0))]
+
+
+def main_mesh(cfg):
+    """--attack GeoA3_mesh: the harness of the reference's main_attack.py for its unpublished mesh attacker -- per
+    successful instance Mesh/<name>.obj and Mat/<name>.mat with `vert` / `faces` (main_attack.py:283-293), the name of
+    :287 with the label a FRESH surface draw of the adversarial mesh is classified as (the loop's fixed draw cannot
+    certify itself), and attack_result.txt."""
+    from geoa3_amd import mesh
+    from geoa3_amd.mesh_attack import attack_mesh, refuse_unsupported
+
+    refuse_unsupported(cfg, int(os.environ.get("WORLD_SIZE", "1")))
+    if cfg.attack_label not in ("Untarget", "Random"):
+        raise ValueError("--attack GeoA3_mesh takes --attack_label Untarget or Random, not %r" % cfg.attack_label)
+    if cfg.arch not in ARCHS:
+        raise AssertionError("Not support such arch.")
+    device = torch.device("cuda", 0)
+    say = (lambda *a: None) if cfg.quiet else print
+    saved_dir = saved_dir_name(cfg)
+    for sub in ("Mesh", "Mat", "Records"):
+        os.makedirs(os.path.join(saved_dir, sub), exist_ok=True)
+    say("==>Successfully created {}".format(saved_dir))
+    seed = 0 if cfg.id == 0 else int(time.time())
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    torch.cuda.manual_seed_all(seed)
+    net, _ = load_victim(cfg, device, say)
+    items = load_meshes(cfg)
+    num_attack_success, cnt_all, t_attack = 0, 0, 0.0
+    batches = [items[i:i + cfg.batch_size] for i in range(0, len(items), cfg.batch_size)]
+    for i, batch in enumerate(batches):
+        packed = mesh.pack_meshes([(v, f) for _, v, f, _ in batch], device)
+        with torch.no_grad():      # the clean prediction: the label of a synthetic mesh
+            clean_pred = net(mesh.sample_surface(packed, cfg.npoint)[0]).argmax(1).cpu().numpy()
+        gt = np.array([clean_pred[k] if lab is None else lab for k, (_, _, _, lab) in enumerate(batch)], np.int64)
+        target = gt if cfg.attack_label == "Untarget" else (gt + np.random.randint(1, cfg.classes, len(gt))) % cfg.classes
+        t0 = time.perf_counter()
+        adv, targeted_label, success, _, _ = attack_mesh(net, packed, torch.from_numpy(gt), torch.from_numpy(target), cfg,
+                                                         i, len(batches), verbose=not cfg.quiet)
+        torch.cuda.synchronize()
+        t_attack += time.perf_counter() - t0
+        adv_meshes = [(adv[k].t().contiguous().cpu().numpy(), batch[k][2]) for k in range(len(batch))]
+        with torch.no_grad():      # re-evaluation on a fresh draw of the adversarial surfaces
+            test_pred = net(mesh.sample_surface(mesh.pack_meshes(adv_meshes, device), cfg.npoint)[0]).argmax(1)
+        for k in range(len(batch)):
+            if bool(success[k]):
+                num_attack_success += 1
+                name = "adv_" + str(cnt_all + k) + "_gt" + str(int(gt[k])) + "_attack" + str(test_pred[k].item()) + \
+                       "_expect" + str(targeted_label[k].item())
+                verts, faces = adv_meshes[k]
+                sio.savemat(os.path.join(saved_dir, "Mat", name + ".mat"), {"vert": verts, "faces": faces})
+                mesh.write_obj(os.path.join(saved_dir, "Mesh", name + ".obj"), verts, faces)
+        cnt_all += len(batch)
+    line = "attack success: {0:.2f}\n".format(num_attack_success / float(max(cnt_all, 1)) * 100)
+    say(line)
+    with open(os.path.join(saved_dir, "attack_result.txt"), "at") as f:
+        f.write(line)
+    say("saved_dir: {0}".format(saved_dir))
+    iters = cfg.binary_max_steps * cfg.iter_max_steps * len(batches)
+    print("attack time: {:.2f} s, {:.1f} inner iterations/s".format(t_attack, iters / max(t_attack, 1e-9)))
+    say("Finish!")
+    return saved_dir
+
+
 def main(cfg):
     import torch.distributed as dist
 
     from geoa3_amd import attack as geoa3_attack
-    from geoa3_amd.data import TEN_LABEL_INDEXES, ModelNet40, synthetic_state_dict, write_synthetic_mat
+    from geoa3_amd.data import TEN_LABEL_INDEXES, ModelNet40, write_synthetic_mat
     from geoa3_amd.utility import estimate_normal_via_ori_normal, farthest_points_sample
 
-    if cfg.attack == "GeoA3_mesh":
-        raise AssertionError("Not uploaded yet.")          # as the reference (main_attack.py:27-28)
+    if cfg.attack == "GeoA3_mesh":                          # (the reference: "Not uploaded yet.", main_attack.py:27-28)
+        return main_mesh(cfg)
     if cfg.arch not in ARCHS:
         raise AssertionError("Not support such arch.")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -327,27 +453,7 @@ def main(cfg):
     elif cfg.is_save_normal:
         raise AssertionError("--is_save_normal needs --dense_data_dir_file (main_attack.py:124,246)")
 
-    say("=>Loading model")
-    model_path = os.path.join("Pretrained", cfg.arch, str(cfg.npoint), "model_best.pth.tar")
-    net = make_victim(cfg)
-    if os.path.isfile(model_path):
-        load_checkpoint(net, cfg, model_path)
-        say("==>Successfully load pretrained-model from {}".format(model_path))
-    elif cfg.synthetic and cfg.arch == "DGCNN":
-        say("==>No checkpoint at {}: the module's own seeded init (--synthetic)".format(model_path))
-    elif cfg.synthetic and cfg.arch == "PointNetPP":
-        with torch.no_grad():   # default-initialised modules (seeded above) with non-trivial BatchNorm statistics
-            for mod in net.modules():
-                if isinstance(mod, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
-                    mod.running_mean.normal_(0, 0.1)
-                    mod.running_var.uniform_(0.5, 1.5)
-        say("==>No checkpoint at {}: seeded random-init weights (--synthetic)".format(model_path))
-    elif cfg.synthetic:
-        net.load_state_dict(synthetic_state_dict(cfg.classes, seed=0, device=device))
-        say("==>No checkpoint at {}: calibrated random-init weights (--synthetic)".format(model_path))
-    else:
-        raise FileNotFoundError(model_path)
-    net = net.to(device).eval()
+    net, model_path = load_victim(cfg, device, say)
 
     if cfg.synthetic and not os.path.isfile(model_path):
         # the reference data file only holds correctly classified shapes (gen_data_mat.py:255-260): mirror that
