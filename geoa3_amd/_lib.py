@@ -184,6 +184,8 @@ SIGNATURES = {
     "geoa3_debug_grid_nn1_pair": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp]),
     "geoa3_debug_knn_self_route": (C.c_int, [C.c_int] * 6),
     "geoa3_debug_geo_route": (C.c_int, [C.POINTER(GeoArgs)]),
+    "geoa3_debug_reg_route": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "geoa3_debug_uniform_route": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int]),
     "geoa3_debug_geo_wide_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "geoa3_debug_geo_wide": (C.c_int, [C.POINTER(GeoArgs), C.c_int, vp]),
     "geoa3_debug_fc": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

@@ -19,8 +19,14 @@
 // bit identical and a row does not depend on the rest of the batch.  The scale is the instance's own: pass 1 takes the
 // largest |term| of the instance (a maximum: order free), the unit is 2^(e - 40) with e its exponent, pass 2 forms the
 // terms again and adds them.  Coefficients and terms are formed in double (B N k pairs: the cost is not arithmetic).
-// A point sums at most N + k terms of at most 2^41 units each: no overflow.  A non-finite term or coordinate, or a
-// neighbour index outside the cloud, makes the whole instance's gradient NaN.
+// A point of a search's table sums at most N + k terms of at most 2^41 units each; a handed-in table may name one point in
+// every entry, which then sums N k + k terms: at most 8192 * 63 + 63 < 2^19 terms, below 2^60 units, no overflow.
+// A non-finite term or coordinate, or a
+// neighbour index outside the cloud, makes the whole instance's gradient NaN (displace_fwd_kernel: an index outside the
+// cloud makes that point's value NaN, the others keep their bits).
+// kNN_smoothing_loss reads distances only: a non-finite distance in columns 1..k of a handed-in table over a finite cloud
+// (any input that makes the threshold NaN) gives the instance loss NaN, mask 0 and gradient NaN -- never a silent
+// "nothing exceeds the threshold".  Column 0 and the columns beyond k are read by no kernel.
 // The sums live in LDS beside the cloud (N <= ~4200); beyond that in the workspace, the cloud read from global memory.
 #include "common.h"
 
@@ -105,6 +111,12 @@ __global__ __launch_bounds__(REG_T) void smooth_fwd_kernel(const float* __restri
     return;
   }
   const float thr = smooth_stats(knn_d + (size_t)b * N * ld, N, k, ld, coef, s_s, s_red);
+  if (thr != thr) {                                     // (the same in every thread: block_sum's result)
+    if (tid == 0) loss[b] = __builtin_nanf("");
+    if (cond)
+      for (int i = tid; i < N; i += REG_T) cond[(size_t)b * N + i] = 0;
+    return;
+  }
   double v = 0.0;
   for (int i = tid; i < N; i += REG_T) {
     const float s = s_s[i];
@@ -226,6 +238,7 @@ __global__ __launch_bounds__(REG_T) void reg_bwd_kernel(RegBwd p) {
   }
   if (MODE == REG_SMOOTH) {
     const float thr = smooth_stats(D, N, k, ld, p.coef, s_s, s_red);
+    bad = bad || thr != thr;                             // (a non-finite distance in the table: the instance is refused below)
     for (int i = tid; i < N; i += REG_T) s_c[i] = s_s[i] > thr ? 1 : 0;
   }
   __syncthreads();                                      // s_s is dead: its space becomes the sums
@@ -411,6 +424,9 @@ size_t reg_lds_bwd(int mode, int N) {   // dynamic LDS of the LDS form
   return (size_t)N * (mode == REG_SMOOTH ? 37 : 36);
 }
 
+// the one predicate of launch_reg_bwd, geoa3_reg_workspace_bytes and geoa3_debug_reg_route
+bool reg_sums_in_lds(int mode, int N) { return reg_lds_bwd(mode, N) <= REG_LDS_MAX; }
+
 int reg_check(int B, int N, int k) {
   if (B <= 0 || N <= 0 || k < 1) return GEOA3_EINVAL;
   if (k + 1 > GEOA3_KNN_MAX_K || N > REG_MAX_N) return GEOA3_ENOSUPPORT;
@@ -452,7 +468,7 @@ int reg_table(const float* cloud, int B, int N, int k, const float** d, const in
 template <int MODE>
 int launch_reg_bwd(RegBwd p, int B, void* ws, hipStream_t s) {
   const size_t lds = reg_lds_bwd(MODE, p.N);
-  if (lds <= REG_LDS_MAX) {
+  if (reg_sums_in_lds(MODE, p.N)) {
     auto kern = reg_bwd_kernel<MODE, true>;
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -472,8 +488,14 @@ int launch_reg_bwd(RegBwd p, int B, void* ws, hipStream_t s) {
 extern "C" int64_t geoa3_reg_workspace_bytes(int B, int N, int k) {
   if (reg_check(B, N, k) != GEOA3_OK) return 0;
   size_t n = 2 * align256((size_t)B * N * (k + 1) * sizeof(float));
-  if (reg_lds_bwd(REG_SMOOTH, N) > REG_LDS_MAX) n += (size_t)B * 3 * N * sizeof(unsigned long long);
+  // (kNN_smoothing_loss has the largest footprint per point: the first mode to leave LDS)
+  if (!reg_sums_in_lds(REG_SMOOTH, N)) n += (size_t)B * 3 * N * sizeof(unsigned long long);
   return (int64_t)n;
+}
+
+extern "C" int geoa3_debug_reg_route(int mode, int N, int k) {
+  if (mode < REG_SMOOTH || mode > REG_NORMAL || reg_check(1, N, k) != GEOA3_OK) return GEOA3_REG_ROUTE_REFUSED;
+  return reg_sums_in_lds(mode, N) ? GEOA3_REG_ROUTE_LDS : GEOA3_REG_ROUTE_WORKSPACE;
 }
 
 extern "C" int geoa3_knn_smoothing_loss(const float* pc, int B, int N, int k, float coef, const float* knn_d,

@@ -324,6 +324,9 @@ int uniform_plan(int B, int N, const double* percentages, int P, double radius, 
   return GEOA3_OK;
 }
 
+// the one predicate of launch_uniform_main and geoa3_debug_uniform_route
+int uniform_route(const UniformPlan& pl) { return pl.lds_acc ? GEOA3_UNIFORM_ROUTE_LDS : GEOA3_UNIFORM_ROUTE_WORKSPACE; }
+
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // workspace: [partial B x UNI_MAX_P double] [xyz B x N x 3 float] [fps B x N int] [acc B x 3N int64 (large clouds)]
@@ -349,7 +352,7 @@ UniformWs uniform_ws(void* ws, int B, int N) {
 template <int KP, bool CT>
 int launch_uniform_main(const UniformPlan& pl, const float* pc, int B, int N, const UniformWs& w, float* grad,
                         int32_t* group_idx, hipStream_t s) {
-  if (pl.lds_acc) {
+  if (uniform_route(pl) == GEOA3_UNIFORM_ROUTE_LDS) {
     auto kern = uniform_main_kernel<KP, CT, true>;
     if (pl.lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
@@ -376,6 +379,12 @@ extern "C" int64_t geoa3_uniform_loss_workspace_bytes(int B, int N) {
   const size_t lds_all = (size_t)N * 3 * sizeof(float) + (size_t)UNI_WAVES * UNI_MAX_NS * sizeof(int) + (size_t)N * 3 * 8;
   if (lds_all > UNI_LDS_MAX) n += (size_t)B * 3 * N * sizeof(unsigned long long);
   return (int64_t)n;
+}
+
+extern "C" int geoa3_debug_uniform_route(int B, int N, const double* percentages, int P, double radius, int k) {
+  UniformPlan pl;
+  const int rc = uniform_plan(B, N, percentages, P, radius, k, &pl);
+  return rc != GEOA3_OK ? rc : uniform_route(pl);
 }
 
 extern "C" int geoa3_uniform_loss(const float* pc, int B, int N, const double* percentages, int num_percentages,

@@ -121,6 +121,23 @@ int geoa3_debug_knn_self_route(int B, int N, int K, int method, int has_prior, i
 #define GEOA3_GEO_ROUTE_REFUSED 5   /* geoa3_geo_loss_grad returns GEOA3_ENOSUPPORT */
 int geoa3_debug_geo_route(const geoa3_geo_args* args);
 
+/* Where reg_bwd_kernel (the gradients of geom_reg.hip) keeps the per-point fixed-point sums of a cloud of N points with k
+ * neighbours: in LDS beside the cloud, or in the workspace (geoa3_reg_workspace_bytes then includes them).  mode: 0 =
+ * kNN_smoothing_loss, 1 = repulsion_loss, 2 = displacement_loss, 3 = corresponding_normal_loss.  REFUSED where the entry
+ * points refuse the sizes (or the mode is none of the four).  Both forms return the same bits.  No GPU work
+ * (tests/test_reg_route.py). */
+#define GEOA3_REG_ROUTE_LDS 0         /* reg_bwd_kernel<mode, true> */
+#define GEOA3_REG_ROUTE_WORKSPACE 1   /* reg_bwd_kernel<mode, false> */
+#define GEOA3_REG_ROUTE_REFUSED 2
+int geoa3_debug_reg_route(int mode, int N, int k);
+
+/* The same for uniform_main_kernel (geoa3_uniform_loss, geom_uniform.hip): LDS or WORKSPACE
+ * (geoa3_uniform_loss_workspace_bytes then includes the sums), or the error code (negative) geoa3_uniform_loss returns for
+ * these sizes.  percentages: P doubles on the host.  No GPU work. */
+#define GEOA3_UNIFORM_ROUTE_LDS 0         /* uniform_main_kernel<*, *, true> */
+#define GEOA3_UNIFORM_ROUTE_WORKSPACE 1   /* uniform_main_kernel<*, *, false> */
+int geoa3_debug_uniform_route(int B, int N, const double* percentages, int P, double radius, int k);
+
 /* The two-pass kernels behind GEOA3_GEO_ROUTE_WIDE on a cloud of any size from 64 to 8192 points (tests hold them to
  * geo_big_kernel bit for bit where both run).  ranges: owner ranges per instance, 1..16; 0 = the dispatcher's choice (the
  * fewest that fit LDS).  The gradient does not depend on it.  GEOA3_ENOSUPPORT when that many ranges do not fit LDS.
