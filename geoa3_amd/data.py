@@ -224,6 +224,37 @@ def synthetic_cad_clouds(M: int, N: int, seed: int = 0, duplicates: float = 0.05
     return data.contiguous().float(), normal.contiguous().float()
 
 
+def augment_batch(points: torch.Tensor, generator: torch.Generator = None, up_axis: int = 1) -> torch.Tensor:
+    """The training augmentation of Provider/modelnet_trn_test.py:60-73 (`_augment_batch_data`, provider.py) as batched torch
+    on the tensor's own device (GPU or CPU), drawn from `generator` (a generator of that device; None: the global one):
+    points [B,N,3] -> [B,N,3], per cloud a rotation about the up axis by U(0, 2 pi), a perturbation rotation Rz Ry Rx with
+    angles clip(0.06 N(0,1), +-0.18), a scale U(0.8, 1.25) and a shift U(-0.1, 0.1)^3; per point a jitter
+    clip(0.01 N(0,1), +-0.05); one shuffle of the point order for the whole batch.  The reference's distributions, not
+    numpy's draws.  The input is not modified."""
+    B, N, _ = points.shape
+    dev, dt = points.device, points.dtype
+    rand = lambda *s: torch.rand(*s, device=dev, dtype=dt, generator=generator)
+    randn = lambda *s: torch.randn(*s, device=dev, dtype=dt, generator=generator)
+
+    def axis_rotation(angle, axis):
+        """[B,3,3]: the reference's matrices -- about y [[c,0,s],[0,1,0],[-s,0,c]], about x [[1,0,0],[0,c,-s],[0,s,c]],
+        about z [[c,-s,0],[s,c,0],[0,0,1]]"""
+        c, s = torch.cos(angle), torch.sin(angle)
+        i, j = [(1, 2), (2, 0), (0, 1)][axis]
+        R = torch.eye(3, device=dev, dtype=dt).repeat(B, 1, 1)
+        R[:, i, i], R[:, j, j], R[:, i, j], R[:, j, i] = c, c, -s, s
+        return R
+
+    up = axis_rotation(rand(B) * (2 * np.pi), up_axis)
+    ang = (0.06 * randn(B, 3)).clamp(-0.18, 0.18)
+    pert = axis_rotation(ang[:, 2], 2) @ axis_rotation(ang[:, 1], 1) @ axis_rotation(ang[:, 0], 0)
+    out = (points @ up) @ pert                                   # row vectors times the matrix, as np.dot(pc, R)
+    out = out * (0.8 + 0.45 * rand(B)).view(B, 1, 1)
+    out = out + (rand(B, 3) * 0.2 - 0.1).view(B, 1, 3)
+    out = out + (0.01 * randn(B, N, 3)).clamp(-0.05, 0.05)
+    return out[:, torch.randperm(N, device=dev, generator=generator)]
+
+
 SYNTHETIC_GENERATORS = {"ellipsoid": synthetic_clouds, "cad": synthetic_cad_clouds}
 
 

@@ -238,10 +238,23 @@ class _TransformNet(nn.Module):
             self.fc3.weight.zero_()
             self.fc3.bias.copy_(torch.eye(K).view(-1))
 
+    def forward_train(self, x: Tensor, wide_train: str) -> Tensor:
+        """transform_net.forward in training mode (Model/PointNet.py:78-87): plain torch on the module's own parameters,
+        conv3 -> bn3 -> relu -> max through geoa3_amd.pointnet_train (the fused HIP layer, or its plain composition)."""
+        from .pointnet_train import wide_layer_train
+        f = torch.relu(self.bn1(self.conv1(x)))
+        f = torch.relu(self.bn2(self.conv2(f)))
+        f = wide_layer_train(f, self.conv3, self.bn3, relu=True, mode=wide_train)
+        f = torch.relu(self.bn4(self.fc1(f)))
+        f = torch.relu(self.bn5(self.fc2(f)))
+        return self.fc3(f).view(f.size(0), self.K, self.K)
+
 
 class PointNet(nn.Module):
-    """Drop-in for Model.PointNet.PointNet(classes, return_idx=False, npoint=1024) in EVAL mode.
-    `net.load_state_dict(torch.load(path)['state_dict'])` works unchanged (main_attack.py:144-145)."""
+    """Drop-in for Model.PointNet.PointNet(classes, return_idx=False, npoint=1024).
+    `net.load_state_dict(torch.load(path)['state_dict'])` works unchanged (main_attack.py:144-145).
+    Eval mode: the HIP library's forward and input gradient.  Training mode (main_train.py): `(logits, transform)` as the
+    reference returns them, the three 1024-wide layers through geoa3_amd.pointnet_train, the rest plain torch operators."""
 
     def __init__(self, classes: int, return_idx: bool = False, npoint: int = 1024):
         super().__init__()
@@ -257,6 +270,10 @@ class PointNet(nn.Module):
         self.fc1, self.bn6 = nn.Linear(1024, 512), nn.BatchNorm1d(512)
         self.fc2, self.bn7 = nn.Linear(512, 256), nn.BatchNorm1d(256)
         self.fc3 = nn.Linear(256, classes)
+        self.drop1, self.drop2 = nn.Dropout(p=0.3), nn.Dropout(p=0.3)   # Model/PointNet.py:127-128 (no state_dict entries)
+        # training mode's 1024-wide layers: 'fused' (the HIP layer of pointnet_train.py: a third of the step's peak memory) |
+        # 'torch' (the plain composition; the default: at B 32, N 1024 the fused STEP is slower)
+        self.wide_train = "torch"
         with torch.no_grad():  # Model/PointNet.py:162-164
             for m in (self.conv1, self.conv2, self.conv3, self.conv4, self.conv5, self.fc1, self.fc2, self.fc3):
                 nn.init.xavier_uniform_(m.weight)
@@ -296,10 +313,33 @@ class PointNet(nn.Module):
     def forward(self, pc: Tensor) -> Tensor:
         assert pc.size(1) == 3
         if self.training:
-            raise NotImplementedError("only the eval-mode forward (the attack's victim) is implemented")
+            return self._forward_train(pc)
         if torch.compiler.is_compiling():   # traced: the registered custom op (geoa3_amd/library.py), same kernels
             return torch.ops.geoa3.pointnet_forward(pc, self._handle)
         return _PointNetFn.apply(pc, self.packed(pc.device), self._ws_cache)
+
+    def _forward_train(self, pc: Tensor):
+        """Model/PointNet.py:132-155 in training mode -> (logits, transform [B,64,64])."""
+        from .pointnet_train import wide_layer_train
+        t3 = self.input_transform.forward_train(pc, self.wide_train)
+        f = torch.bmm(pc.permute(0, 2, 1), t3).permute(0, 2, 1)
+        f = torch.relu(self.bn1(self.conv1(f)))
+        f = torch.relu(self.bn2(self.conv2(f)))
+        transform = self.feature_transform.forward_train(f, self.wide_train)
+        f = torch.bmm(f.permute(0, 2, 1), transform).permute(0, 2, 1)
+        f = torch.relu(self.bn3(self.conv3(f)))
+        f = torch.relu(self.bn4(self.conv4(f)))
+        f = wide_layer_train(f, self.conv5, self.bn5, relu=True, mode=self.wide_train)
+        f = self.drop1(torch.relu(self.bn6(self.fc1(f))))
+        f = self.drop2(torch.relu(self.bn7(self.fc2(f))))
+        return self.fc3(f), transform
+
+    def adjust_bn_momentum(self, epoch: int, bn_momentum: float) -> None:
+        """Model/PointNet.py:166-179: every BatchNorm's momentum = max(bn_momentum * 0.5^(epoch // 20), 0.01)."""
+        momentum = max(bn_momentum * (0.5 ** (epoch // 20)), 0.01)
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm1d):
+                m.momentum = momentum
 
     @property
     def classes(self) -> int:

@@ -829,6 +829,36 @@ int geoa3_reg_fold(const float* loss, const float* grad, float w, int B, int N, 
 int geoa3_reg_fold_points(const float* out, const float* grad, float w, int B, int N, float* term, float* constrain,
                           int constrain_add, float* g, int g_add, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A 1024-wide PointNet layer in TRAINING mode: conv(128 -> 1024, taps 1 | 3, zero padding taps / 2) -> BatchNorm1d with
+ * batch statistics -> [relu] -> max over points, without writing the [B,1024,N] activation.  Replaces
+ * Model/PointNet.py:81-82 (transform_net: `F.relu(self.bn3(self.conv3(x)))`, `torch.max(x, 2, keepdim=True)[0]`) and
+ * Model/PointNet.py:146-147 (`F.relu(self.bn5(self.conv5(x)))`, `torch.max(x, 2, keepdim=True)[0]`) under net.train().
+ * X [B,128,N]; W [1024, taps*128] with k = tap*128 + ci; U[b,:,p] is the unfolded input column (zeros past the ends).
+ * The conv bias is not an argument: BatchNorm removes it from the output and from every gradient (its gradient is zero).
+ * Limits: B <= 65535, 2 <= B*N < 2^24 (GEOA3_EINVAL otherwise: B*N < 2 has no batch variance, as torch refuses it).
+ * Sums are taken in an order that depends on (B, N) only: repeated calls give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+int64_t geoa3_wide_train_workspace_bytes(int B, int N, int taps);
+/* Forward.  shift [1024]: the caller's estimate of the mean of W U per channel (W mean(U) is exact up to rounding); the
+ * variance is accumulated about it.  Writes, with a[b,c] the first maximum of y = W U over the points where gamma[c] > 0,
+ * the first minimum where gamma[c] < 0, point 0 where gamma[c] == 0:
+ *   arg [B,1024] = a,  xhat [B,1024] = (y[a] - mean) / sqrt(var + eps),  out = gamma xhat + beta, relu'd when `relu`,
+ *   mean [1024] = mean of W U over all B*N positions (add the conv bias for BatchNorm's running_mean), var [1024] = the
+ *   biased variance.  A non-finite activation makes mean, var and every out[:, c] / xhat[:, c] it enters NaN.
+ * workspace: geoa3_wide_train_workspace_bytes(B, N, taps) bytes, 256-byte aligned. */
+int geoa3_wide_train_forward(const float* X, const float* W, const float* shift, const float* gamma, const float* beta,
+                             float eps, int relu, int B, int N, int taps, float* out, int32_t* arg, float* xhat,
+                             float* mean, float* var, void* workspace, void* stream);
+/* Backward of Model/PointNet.py:81-82 / :146-147, the term through the selected points:
+ * dW [1024, taps*128] = sum_b coef[b,c] U[b,:,arg[b,c]], b ascending (coef [B,1024] = gated upstream gradient * gamma / sigma). */
+int geoa3_wide_train_gather(const float* X, const float* coef, const int32_t* arg, int B, int N, int taps, float* dW,
+                            void* stream);
+/* ... and its input gradient: dX [B,128,N] (every element written) = sum over (c, tap) with arg[b,c] + tap - taps/2 == q
+ * of coef[b,c] W[c, tap*128 + ci], in ascending (c, tap) order. */
+int geoa3_wide_train_scatter(const float* W, const float* coef, const int32_t* arg, int B, int N, int taps, float* dX,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
