@@ -195,6 +195,9 @@ SIGNATURES = {
     "geoa3_debug_geo_wide": (C.c_int, [C.POINTER(GeoArgs), C.c_int, vp]),
     "geoa3_debug_fc": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "geoa3_debug_conv_cm": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "geoa3_debug_conv_chain": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "geoa3_debug_conv_cm_ex": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, vp, vp, C.c_int,
+                                         C.c_int, C.c_int, vp]),
     "geoa3_debug_wide_bwd_conv": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int,
                                             C.c_int, C.c_int, vp]),
     "geoa3_debug_gram64": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),

@@ -160,10 +160,11 @@ struct Call {
   // Y = act(W relu(w1 (T^T x) + b1) + bias): the 3-channel first layer (Model/PointNet.py:79,137-139) folded into the
   // 64-input convolution that follows it; its activation is never written
   int conv_first(const float* x, const float* T, const float* w1, const float* b1, const float* W, const float* bias,
-                 float* Y, int Co, unsigned long long* Ymask) const {
+                 float* Y, int Co, unsigned long long* Ymask, unsigned long long* poison_keys = nullptr) const {
     ConvArgs a{};
     a.split = plan.split;
     a.Ymask = Ymask;
+    a.poison_keys = poison_keys;
     a.x3 = x; a.T3 = T; a.w1 = w1; a.b1 = b1; a.produce_first = 1;
     a.W = W; a.sWb = 0; a.sWco = 64; a.sWk = 1;
     a.bias = bias;
@@ -244,10 +245,11 @@ struct Call {
       else if (plan.chain) {   // conv1 + conv2 of the 3-channel T-Net: the chain kernel with one stage
         ConvChainArgs a{};
         a.x3 = x3; a.w1 = t.w1; a.b1 = t.b1;
+        a.poison_keys = w.keys;   // the first kernel that reads the cloud: the non-finite rule (pn_poison_keys)
         a.N = N; a.B = B; a.ns = 1;
         a.st[0] = ChainStage{t.w2, 0, t.b2, u.act128, (long)128 * N, u.m128, 128};
         TRY(launch_conv_chain(a, s));
-      } else TRY(conv_first(x3, nullptr, t.w1, t.b1, t.w2, t.b2, u.act128, 128, u.m128));
+      } else TRY(conv_first(x3, nullptr, t.w1, t.b1, t.w2, t.b2, u.act128, 128, u.m128, w.keys));
     }
     TRY(wide(u.act128, t.w3p, t.w3h, t.w3h_unscale, t.b3, u.pooled, u.arg, 1, u.hits, u.hoff));
     TRY(fc(u.pooled, 1024, t.f1, t.fb1, u.f4, 512, B, true, nullptr, s));
@@ -329,7 +331,7 @@ struct Call {
     TRY(wide(w.h4, p.w5p, p.w5h, p.w5h_unscale, p.b5, w.p5, w.i5, 3, w.hl5, w.ho5));
     TRY(fc(w.p5, 1024, p.f1, p.fb1, w.f6, 512, B, true, nullptr, s));
     TRY(fc(w.f6, 512, p.f2, p.fb2, w.f7, 256, B, true, nullptr, s));
-    return fc(w.f7, 256, p.f3, p.fb3, logits, p.classes, B, false, nullptr, s);
+    return fc(w.f7, 256, p.f3, p.fb3, logits, p.classes, B, false, nullptr, s, nullptr, w.T3, 9);   // NaN where T3[b] is
   }
 
   // ---- the backward's stages, in order --------------------------------------------------------------------------------
@@ -461,6 +463,25 @@ extern "C" int geoa3_pointnet_backward(const geoa3_pointnet_weights* pw, const f
   TRY(c.bwd_feature_transform_grad());
   TRY(c.plan.chain ? c.bwd_trunk_front_chain(x, dx) : c.bwd_trunk_front_layers(x, dx));
   return c.bwd_input_transform(x, dx);
+}
+
+// ------------------------------------------------------------------------------------------
+// The forward's chain kernels in isolation (geoa3_hip_debug.h; tests/test_gpu_pointnet_fwd.py): the args struct as
+// tnet_tail_fwd / fwd_trunk_front / fwd_conv3_conv4 fill it, then the launcher -- nothing else.
+// ------------------------------------------------------------------------------------------
+extern "C" int geoa3_debug_conv_chain(const float* X, const float* x3, const float* T3, const float* w1, const float* b1,
+                                      int ns, const float* const* W, const int64_t* sWb, const float* const* bias,
+                                      float* const* Y, void* const* Ymask, int B, int N, void* stream) {
+  if (ns < 1 || ns > 3 || !W || !sWb || !bias || !Y || !Ymask || (X && x3)) return GEOA3_EINVAL;
+  ConvChainArgs a{};
+  if (x3) { a.x3 = x3; a.T3 = T3; a.w1 = w1; a.b1 = b1; }
+  else { a.X = X; a.sXb = (long)64 * N; a.ldX = N; }
+  a.N = N; a.B = B; a.ns = ns;
+  for (int i = 0; i < ns; ++i) {
+    const int Co = i + 1 < ns ? 64 : 128;
+    a.st[i] = ChainStage{W[i], (long)sWb[i], bias[i], Y[i], (long)Co * N, static_cast<unsigned long long*>(Ymask[i]), Co};
+  }
+  return launch_conv_chain(a, geoa3_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -13,7 +13,11 @@
 
 namespace {
 
-// d[lane l] = v (wave-uniform value, constant lane): one instruction instead of compare + select
+// d[lane l] = v (wave-uniform value, constant lane): one instruction instead of compare + select.
+// v must come out of a SCALAR instruction.  The compiler does not see into the asm statement, so it puts no wait states
+// between a vector compare that writes an SGPR pair and this read of it, which gfx950 needs: the epilogue's `ballot & livemask`
+// is an s_and_b64 between the two.  With the ballot handed over as it is (v_cmp_lt_f32 s[4:5] directly in front of
+// v_writelane_b32 .., s4) the gate words came out wrong at every N on the MI355X (the fifth mutation).
 __device__ __forceinline__ void cc_writelane(int& d, int v, int l) {
   asm("v_writelane_b32 %0, %1, %2" : "+v"(d) : "s"(v), "n"(l));
 }
@@ -169,6 +173,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if (FIRST) {
     const float* xp = a.x3 + (size_t)b * 3 * a.N + (live ? col : a.N - 1);
     const float x0 = xp[0], x1 = xp[a.N], x2 = xp[2 * (size_t)a.N];
+    if (NS == 1 && a.poison_keys) pn_poison_keys(a.poison_keys, b, x0, x1, x2, live);
     float p0 = x0, p1 = x1, p2 = x2;
     if (a.T3) {   // bmm(pc^T, T)^T : x'[c] = sum_d x[d] T[d][c]   (Model/PointNet.py:138)
       const float* t = a.T3 + (size_t)b * 9;

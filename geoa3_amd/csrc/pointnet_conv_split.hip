@@ -87,6 +87,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCH <= 8 &&
     x0 = xp[0];
     x1 = xp[a.N];
     x2 = xp[2 * (size_t)a.N];
+    if (FIRST && a.poison_keys && rb == 0) pn_poison_keys(a.poison_keys, b, x0, x1, x2, live);
     p0 = x0;
     p1 = x1;
     p2 = x2;

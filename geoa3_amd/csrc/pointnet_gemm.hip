@@ -45,6 +45,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
     x0 = xp[0];
     x1 = xp[a.N];
     x2 = xp[2 * (size_t)a.N];
+    if (FIRST && a.poison_keys && rb == 0) pn_poison_keys(a.poison_keys, b, x0, x1, x2, live);
     p0 = x0;
     p1 = x1;
     p2 = x2;
@@ -340,8 +341,12 @@ __global__ __launch_bounds__(64 * S) void fc_kernel(FcArgs a) {
     const int mr = m0 + (T == 32 ? mfma_row(i, lane) : 4 * g + i);
     if (oc < a.Nout && mr < a.M) {
       v += bias;
-      if (a.relu) v = fmaxf(v, 0.f);
+      if (a.relu) v = v != v ? v : fmaxf(v, 0.f);   // a NaN stays (pn_poison_keys, pointnet_kernels.h)
       if (a.Z) v = a.Z[(size_t)mr * a.ldZ + oc] > 0.f ? v : 0.f;
+      if (a.poison) {
+        const float pz = a.poison[(size_t)mr * a.ldP];
+        v = pz != pz ? pz : v;
+      }
       a.Y[(size_t)bz * a.sYb + (size_t)mr * a.ldY + oc] = v;
     }
   };
@@ -382,7 +387,7 @@ __global__ __launch_bounds__(64) void fc_ksplit_reduce_kernel(FcArgs a) {
     const int mr = m0 + (T == 32 ? mfma_row(i, lane) : 4 * g + i);
     if (oc < a.Nout && mr < a.M) {
       v += bias;
-      if (a.relu) v = fmaxf(v, 0.f);
+      if (a.relu) v = v != v ? v : fmaxf(v, 0.f);
       if (a.Z) v = a.Z[(size_t)mr * a.ldZ + oc] > 0.f ? v : 0.f;
       a.Y[(size_t)mr * a.ldY + oc] = v;
     }
@@ -425,6 +430,24 @@ extern "C" int geoa3_debug_conv_cm(const float* X, const float* W, const float* 
   a.W = W; a.sWb = 0; a.sWco = K; a.sWk = 1;
   a.bias = bias;
   a.Z = Z; a.sZb = (long)Co * N; a.ldZ = N;
+  a.Y = Y; a.sYb = (long)Co * N; a.ldY = N;
+  a.Co = Co; a.K = K; a.N = N; a.B = B;
+  a.relu = relu;
+  return launch_conv_cm(a, geoa3_stream(stream));
+}
+
+// the forward forms (geoa3_hip_debug.h): the arguments as Call::conv / conv_first / fwd_conv3_conv4 of pointnet.hip fill them
+extern "C" int geoa3_debug_conv_cm_ex(const float* X, const float* x3, const float* T3, const float* w1, const float* b1,
+                                      int K, int Co, const float* W, int64_t sWb, const float* bias, int relu, float* Y,
+                                      void* Ymask, int split, int B, int N, void* stream) {
+  if ((!X && !x3) || (X && x3) || !W || !Y || B <= 0 || N <= 0) return GEOA3_EINVAL;
+  ConvArgs a{};
+  a.split = split;
+  a.Ymask = static_cast<unsigned long long*>(Ymask);
+  if (x3) { a.x3 = x3; a.T3 = T3; a.w1 = w1; a.b1 = b1; a.produce_first = 1; }
+  else { a.X = X; a.sXb = (long)K * N; a.ldX = N; }
+  a.W = W; a.sWb = (long)sWb; a.sWco = K; a.sWk = 1;
+  a.bias = bias;
   a.Y = Y; a.sYb = (long)Co * N; a.ldY = N;
   a.Co = Co; a.K = K; a.N = N; a.B = B;
   a.relu = relu;

@@ -10,9 +10,10 @@
 
 // Y[M][Nout] = act(X[M][K] W[Nout][K]^T + bias), gated by Z > 0 when given (FcArgs::kscratch: see there)
 static inline int fc(const float* X, int K, const float* W, const float* bias, float* Y, int Nout, int M, bool relu,
-                     const float* Z, hipStream_t s, float* kscratch = nullptr) {
+                     const float* Z, hipStream_t s, float* kscratch = nullptr, const float* poison = nullptr, int ldP = 0) {
   FcArgs a{};
   a.kscratch = kscratch;
+  a.poison = poison; a.ldP = ldP;
   a.X = X; a.ldX = K;
   a.W = W; a.ldW = K;
   a.bias = bias;

@@ -53,6 +53,9 @@ struct ConvArgs {
   // [Co][16 img_kc] (geoa3_pn2ssg_pack_images: [row >> 5][k >> 4][piece][lane][8 halves]); this launch's K-slice starts
   // at k-step img_c0; Wun[0] = 1 / the image's power-of-two scale.  W is unused then.
   const void* Wimg; const float* Wun; int img_kc, img_c0;
+  // produce_first, the launch that reads the cloud FIRST (T-Net 3): the arg-max keys [B][1024] of the 1024-wide layer behind it,
+  // raised for a cloud with a NaN / Inf coordinate (pn_poison_keys below); null = no check
+  unsigned long long* poison_keys;
 };
 int launch_conv_cm(const ConvArgs& a, hipStream_t s);         // dispatches on a.split
 // The folded first layer before its relu, w = (w1 row, b1), p = T^T x: the ONE expression of every kernel that produces the
@@ -76,8 +79,22 @@ struct ConvChainArgs {
   const float* x3; const float* T3; const float* w1; const float* b1;
   int N, B, ns;
   ChainStage st[3];
+  unsigned long long* poison_keys;            // as ConvArgs::poison_keys (ns = 1: T-Net 3's launch)
 };
 int launch_conv_chain(const ConvChainArgs& a, hipStream_t s);
+// The non-finite rule of geoa3_pointnet_forward (geoa3_hip.h).  Every relu of the trunk is fmaxf, which drops a NaN, so a cloud
+// with a NaN / Inf coordinate would come out as finite logits.  The kernel that reads the cloud first looks at the bits and
+// raises the cloud's 1024 arg-max keys to ~0 (wide_poison's form, wide_unit.h): the finalize pass of T-Net 3's 1024-wide layer
+// then writes NaN pooled features and leaves the keys zero as always, the FC kernel's relu keeps a NaN, and T3[b] is NaN -- the
+// cloud's flag in the workspace: the forward's last FC launch writes NaN logits for it, the backward's dx = T3 q is NaN in every
+// point.  No launch, no buffer, and no instruction of a finite cloud's arithmetic changes.  One wavefront = 64 points.
+__device__ __forceinline__ void pn_poison_keys(unsigned long long* keys, int b, float x0, float x1, float x2, bool live) {
+  const unsigned e0 = __float_as_uint(x0) & 0x7f800000u, e1 = __float_as_uint(x1) & 0x7f800000u,
+                 e2 = __float_as_uint(x2) & 0x7f800000u;
+  const bool bad = live && (e0 == 0x7f800000u || e1 == 0x7f800000u || e2 == 0x7f800000u);
+  if (__builtin_amdgcn_ballot_w64(bad) != 0ull)   // wave-uniform, never taken for a finite cloud
+    for (int c = threadIdx.x & 63; c < 1024; c += 64) atomicMax(keys + (size_t)b * 1024 + c, ~0ull);
+}
 // the backward counterpart (pointnet_conv_chain.hip): dh2 = gate( Wa[b]^T Xa + Wb^T Xb ), then conv_gate_first's form with
 // W2t -- dx [B][3][N] written, dTpart [B][ceil(N/256)][GEOA3_DT_PITCH] partial sums; dh2 is never written
 struct ConvBwdChainArgs {
@@ -105,6 +122,8 @@ struct FcArgs {
   float* Y; int ldY;
   int M, Nout, K;
   int relu;
+  const float* poison; int ldP;               // optional: row m of Y is NaN where poison[m * ldP] is (the non-finite rule of
+                                              // geoa3_pointnet_forward: the logits of a cloud whose T3 is NaN)
   float* kscratch;                            // optional: ceil(Nout/16) * ceil(M/16) * 4096 floats -- K >= 2048 is then split
                                               // over four workgroups per tile (same sums, same order)
 };

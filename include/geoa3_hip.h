@@ -318,7 +318,12 @@ typedef struct geoa3_pointnet_weights {  /* PointNet, Model/PointNet.py:96-160 *
 int64_t geoa3_pointnet_workspace_bytes(int B, int N, int classes);
 
 /* logits[B,classes] = net(x[B,3,N]); keeps the activations backward needs in `workspace`.
- * Replaces `net(input_curr_iter)` at Attacker/geoA3_attack.py:103 (and the b batch-1 calls at :297). */
+ * Replaces `net(input_curr_iter)` at Attacker/geoA3_attack.py:103 (and the b batch-1 calls at :297).
+ * Non-finite points (the rule of geoa3_pn2ssg_forward, and the reference's own outcome: relu(NaN) = NaN, the max keeps it):
+ * a cloud with a NaN or infinite coordinate gets NaN in all of its logits, and geoa3_pointnet_backward gives NaN in all of
+ * its dx under finite dlogits; the other clouds of the batch keep every bit of the result they have without it.  The
+ * cloud's flag is its T3 [9] in the workspace (NaN), raised through the arg-max keys by the first kernel that reads the
+ * cloud: no extra launch, the same under graph replay and with GEOA3_PN_KEYS_CLEAN. */
 int geoa3_pointnet_forward(const geoa3_pointnet_weights* w, const float* x, int B, int N,
                            float* logits, void* workspace, void* stream);
 

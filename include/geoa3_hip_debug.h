@@ -49,6 +49,30 @@ int geoa3_debug_conv_cm(const float* X, const float* W, const float* bias, const
                         int Co, int relu, int split /* 1: split-fp16 operands */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The trunk kernels of geoa3_pointnet_forward one at a time (tests/test_gpu_pointnet_fwd.py).  Each entry fills the launch
+ * arguments the way the forward does and starts the kernel.  A layer is Y [B,Co,N] = relu(W[b] h + bias), W [Co][K] with k
+ * contiguous and sWb floats between the instances' matrices (0 = shared); its input h is X [B,K,N] or -- cloud form, K = 64,
+ * x3 given and X NULL -- the folded first layer relu(w1 (T3^T x3) + b1) with x3 [B,3,N], T3 [B,9] (NULL = identity), w1
+ * [64,3], b1 [64].  Ymask: the layer's gate bits (Y > 0), [B][ceil(N/64)][Co] 64-bit words as below; exactly these words are
+ * written, and the bits of columns >= N in an instance's last word are unspecified.  The tests hold every stored value to
+ * |got - ref| <= 4 sqrt(n) 2^-24 mag + 2^-22 |ref| of a float64 evaluation (n = the terms of the longest sum, mag = the sum
+ * of the absolute products, the input's own bound carried through |W|), every gate bit to the float64 gate wherever the
+ * pre-activation is farther from zero than that bound, and the bits of a stored activation to Y > 0 exactly.
+ * ------------------------------------------------------------------------------------------ */
+/* One launch of conv_chain_kernel (pointnet_conv_chain.hip): ns stages of 64 inputs, the last with 128 outputs, the others 64.
+ * The forward's three forms are the ones that exist: cloud form with ns = 1 or 3, X form with ns = 2 (GEOA3_ENOSUPPORT
+ * otherwise).  W, sWb, bias, Y, Ymask: host arrays of ns entries; Y[i] NULL = stage i leaves gate bits only.  With shared
+ * weights every stage gives the bits of the geoa3_debug_conv_cm_ex launches (split = 1) it replaces. */
+int geoa3_debug_conv_chain(const float* X, const float* x3, const float* T3, const float* w1, const float* b1, int ns,
+                           const float* const* W, const int64_t* sWb, const float* const* bias, float* const* Y,
+                           void* const* Ymask, int B, int N, void* stream);
+/* geoa3_debug_conv_cm with the fields of the forward's launches: the cloud form (produce_first), per-instance weights, the
+ * gate words (NULL = none).  K, Co in {64, 128}; split: 1 = split-fp16 operands (conv_cm64s_kernel), 0 = fp32 (conv_cm64_kernel). */
+int geoa3_debug_conv_cm_ex(const float* X, const float* x3, const float* T3, const float* w1, const float* b1, int K, int Co,
+                           const float* W, int64_t sWb, const float* bias, int relu, float* Y, void* Ymask, int split, int B,
+                           int N, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The kernels of geoa3_pointnet_backward one at a time (tests/test_gpu_pointnet_bwd.py).  Each entry fills the launch
  * arguments the way the backward does and starts the kernel(s); gate bit masks are [B][ceil(N/64)][C] 64-bit words, bit j
  * of word (w, row) = column 64 w + j (bits of columns >= N are ignored).

@@ -285,6 +285,39 @@ def test_wide_layer_shipped_packing_against_float64(taps, N):
     assert torch.isnan(o[2]).all() and torch.isnan(o[4]).all() and torch.isfinite(o[[0, 1, 3]]).all()
 
 
+@pytest.mark.parametrize("no_chain", [0, 2])
+@pytest.mark.parametrize("N", [77, 300])
+@pytest.mark.parametrize("value", [float("nan"), float("inf")])
+def test_nonfinite_point_is_loud(net, N, value, no_chain, monkeypatch):
+    """The non-finite rule of geoa3_pointnet_forward (include/geoa3_hip.h), the one PointNet++ has here and the reference's own
+    forward outcome (relu(NaN) = NaN and the max keeps it): a NaN or +inf in ONE coordinate of cloud 1 of three makes all of
+    its logits NaN and, under a finite dlogits, all of its input gradient; clouds 0 and 2 keep the bits of the clean run.
+    Both arithmetic modes (the fixture), chain and layer-by-layer route, and the clean run again afterwards (the keys
+    that carried the flag are left zero)."""
+    from geoa3_amd import pointnet as PN
+    monkeypatch.setattr(PN, "AB_FLAGS", no_chain)
+    pc, _ = O.make_synthetic_clouds(3, N, seed=N + 1)
+    w = torch.randn(3, 40, generator=torch.Generator().manual_seed(4)).cuda()
+
+    def run(cloud):
+        x = cloud.cuda().requires_grad_()
+        lg = net(x)
+        (lg * w).sum().backward()
+        return lg.detach().clone(), x.grad.clone()
+
+    lg0, g0 = run(pc)
+    assert torch.isfinite(lg0).all() and torch.isfinite(g0).all()
+    bad = pc.clone()
+    bad[1, 2, N // 3] = value
+    lg, g = run(bad)
+    assert torch.isnan(lg[1]).all(), lg[1]
+    assert torch.isnan(g[1]).all(), int(torch.isnan(g[1]).sum())
+    for b in (0, 2):
+        assert torch.equal(lg[b], lg0[b]) and torch.equal(g[b], g0[b]), b
+    lg2, g2 = run(pc)
+    assert torch.equal(lg2, lg0) and torch.equal(g2, g0)
+
+
 @pytest.mark.parametrize("K,Co,N,gate", [(64, 64, 1024, False), (64, 128, 300, False), (128, 64, 1000, True),
                                         (64, 64, 77, True), (128, 128, 256, False)])
 def test_narrow_convolution_both_modes_against_float64(K, Co, N, gate):
