@@ -174,6 +174,11 @@ SIGNATURES = {
                                            vp, vp, vp, vp]),
     "geoa3_wide_train_gather": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_wide_train_scatter": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "geoa3_edge_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "geoa3_edge_train_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
+                                           vp, vp, vp, vp]),
+    "geoa3_edge_train_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                        vp, vp, vp]),
     "geoa3_debug_wide_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "geoa3_debug_wide_fwd": (C.c_int, [vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "geoa3_pn2_group_points_grad_sums": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

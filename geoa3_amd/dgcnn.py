@@ -9,7 +9,10 @@ EVAL-mode forward runs the dynamic-graph part in the HIP library:
                edge tensor never exists, and the backward (geoa3::edge_max_grad) sums in a fixed order
     conv5, pooling and the head: torch operators on the folded weights.
 
-There is no training-mode forward (batch statistics, dropout): it raises, as PointNet.forward does.
+The training-mode forward (batch statistics, dropout) raises by default, as before; `net.edge_train = "fused"` or "torch"
+turns it on: the four EdgeConv layers through geoa3_amd.dgcnn_train.edgeconv_train (the fused HIP layer of
+csrc/edgeconv_train.hip, or the plain materialising torch composition), everything after them through the module's own torch
+layers.
 """
 from __future__ import annotations
 
@@ -64,7 +67,10 @@ def edgeconv(h: Tensor, wa: Tensor, wd: Tensor, t: Tensor, idx: Tensor) -> Tenso
 class DGCNN(nn.Module):
     """DGCNN(k=20, emb_dims=1024, dropout=0.5, output_channels=40): forward(x [B,3,N]) -> logits [B,output_channels] in
     eval mode.  graph_hook(layer, idx), if given, is called with every layer's neighbour table (int64 [B,N,k]); a tensor
-    it returns takes the table's place."""
+    it returns takes the table's place.  edge_train (None | "fused" | "torch"): how a TRAINING-mode forward runs the EdgeConv
+    layers; None, the default, refuses it."""
+
+    edge_train = None       # (a class default: a module pickled before the attribute existed refuses training as it did)
 
     def __init__(self, k: int = 20, emb_dims: int = 1024, dropout: float = 0.5, output_channels: int = 40,
                  graph_hook: Optional[Callable[[int, Tensor], Optional[Tensor]]] = None):
@@ -137,7 +143,9 @@ class DGCNN(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         assert x.dim() == 3 and x.size(1) == 3
         if self.training:
-            raise NotImplementedError("only the eval-mode forward (the attack's victim) is implemented")
+            if self.edge_train is None:
+                raise NotImplementedError("only the eval-mode forward (the attack's victim) is implemented")
+            return self.forward_train(x)
         if not x.is_cuda:
             raise RuntimeError("DGCNN.forward needs a device tensor: the graph search and the EdgeConv layers have no CPU path")
         w = self.folded(x.device)
@@ -158,3 +166,32 @@ class DGCNN(nn.Module):
         z = F.leaky_relu(torch.matmul(z, w["f1"]) + w["fb1"], 0.2)
         z = F.leaky_relu(torch.matmul(z, w["f2"]) + w["fb2"], 0.2)
         return torch.matmul(z, w["f3"]) + w["fb3"]
+
+    def forward_train(self, x: Tensor) -> Tensor:
+        """The training-mode forward (batch statistics, running-statistics updates, dropout) under self.edge_train: the graph
+        of every EdgeConv layer is the K-NN of its own detached input, as in eval mode."""
+        from .dgcnn_train import EDGE_TRAIN_MODES, edgeconv_train
+        if self.edge_train not in EDGE_TRAIN_MODES:
+            raise ValueError("edge_train must be None, 'fused' or 'torch', got %r" % (self.edge_train,))
+        if not x.is_cuda:
+            raise RuntimeError("DGCNN.forward needs a device tensor: the graph search and the EdgeConv layers have no CPU path")
+        h = x.transpose(1, 2).contiguous()                           # [B,N,C] point-major
+        if self.edge_train == "fused":
+            h = h.float()
+        feats = []
+        for l in range(1, 5):
+            hd = h.detach().float()
+            idx = ops.knn_points(hd, hd, K=self.k).idx
+            if self.graph_hook is not None:
+                other = self.graph_hook(l - 1, idx)
+                if other is not None:
+                    idx = other
+            conv = getattr(self, "conv%d" % l)
+            y = edgeconv_train(h, conv[0], conv[1], idx, self.edge_train)
+            feats.append(y)                                         # [B,C',N]
+            h = y.transpose(1, 2).contiguous()
+        z = self.conv5(torch.cat(feats, 1))
+        z = torch.cat((z.max(2)[0], z.mean(2)), 1)
+        z = self.dp1(F.leaky_relu(self.bn6(self.linear1(z)), 0.2))
+        z = self.dp2(F.leaky_relu(self.bn7(self.linear2(z)), 0.2))
+        return self.linear3(z)

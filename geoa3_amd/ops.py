@@ -144,6 +144,64 @@ def edge_max_grad(g: Tensor, y: Tensor, arg: Tensor, idx: Tensor, scratch: Optio
     return dU, dV
 
 
+def edge_train_workspace(B: int, N: int, C_: int, K: int, device) -> Tensor:
+    """Workspace of edge_train / edge_train_grad (geoa3_edge_train_workspace_bytes); the library's refusal raises."""
+    nbytes = int(_lib.load().geoa3_edge_train_workspace_bytes(B, N, C_, K))
+    if nbytes < 0:
+        check(nbytes, "geoa3_edge_train_workspace_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def edge_train(U0: Tensor, V0: Tensor, idx: Tensor, gamma: Tensor, beta: Tensor, eps: float, workspace: Optional[Tensor] = None):
+    """geoa3_edge_train_forward: U0, V0 [B,N,C] float32, idx int64 [B,N,k], gamma, beta [C] -> (y [B,C,N], arg int32 [B,N,C],
+    S1 [B,N,C], mean [C], var [C] (biased), stats float64 [3,C] = mean | var | 1/sqrt(var + eps)): the neighbour half of a
+    training-mode EdgeConv layer, y = lrelu_0.2(gamma r (U0[idx[i, arg]] + V0[i] - mean) + beta)."""
+    B, N, Cc = U0.shape
+    K = idx.shape[2]
+    if tuple(V0.shape) != (B, N, Cc) or tuple(gamma.shape) != (Cc,) or tuple(beta.shape) != (Cc,) or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.Geoa3Error("edge_train: U0 %s, V0 %s, gamma %s, beta %s, idx %s do not fit" % (
+            tuple(U0.shape), tuple(V0.shape), tuple(gamma.shape), tuple(beta.shape), tuple(idx.shape)))
+    if workspace is None:
+        workspace = edge_train_workspace(B, N, Cc, K, U0.device)
+    dev = U0.device
+    y = torch.empty(B, Cc, N, device=dev, dtype=torch.float32)
+    arg = torch.empty(B, N, Cc, device=dev, dtype=torch.int32)
+    S1 = torch.empty(B, N, Cc, device=dev, dtype=torch.float32)
+    mean = torch.empty(Cc, device=dev, dtype=torch.float32)
+    var = torch.empty(Cc, device=dev, dtype=torch.float32)
+    stats = torch.empty(3, Cc, device=dev, dtype=torch.float64)
+    check(_lib.load().geoa3_edge_train_forward(
+        _p(U0, torch.float32), _p(V0, torch.float32), _p(idx, torch.int64), _p(gamma, torch.float32), _p(beta, torch.float32),
+        float(eps), B, N, Cc, K, _p(y), _p(arg), _p(S1), _p(mean), _p(var), _p(stats), _p(workspace), _stream()),
+        "geoa3_edge_train_forward")
+    return y, arg, S1, mean, var, stats
+
+
+def edge_train_grad(g: Tensor, y: Tensor, U0: Tensor, V0: Tensor, arg: Tensor, S1: Tensor, idx: Tensor, gamma: Tensor,
+                    stats: Tensor, workspace: Optional[Tensor] = None):
+    """geoa3_edge_train_grad: g, y [B,C,N]; the forward's inputs and arg, S1, stats -> (dU0, dV0 [B,N,C], dgamma, dbeta [C])."""
+    B, N, Cc = U0.shape
+    K = idx.shape[2]
+    if (tuple(g.shape) != (B, Cc, N) or tuple(y.shape) != (B, Cc, N) or tuple(V0.shape) != (B, N, Cc)
+            or tuple(arg.shape) != (B, N, Cc) or tuple(S1.shape) != (B, N, Cc) or tuple(idx.shape[:2]) != (B, N)
+            or tuple(gamma.shape) != (Cc,) or tuple(stats.shape) != (3, Cc)):
+        raise _lib.Geoa3Error("edge_train_grad: g %s, y %s, U0 %s, V0 %s, arg %s, S1 %s, idx %s, gamma %s, stats %s do not fit" % (
+            tuple(g.shape), tuple(y.shape), tuple(U0.shape), tuple(V0.shape), tuple(arg.shape), tuple(S1.shape),
+            tuple(idx.shape), tuple(gamma.shape), tuple(stats.shape)))
+    if workspace is None:
+        workspace = edge_train_workspace(B, N, Cc, K, U0.device)
+    dev = U0.device
+    dU0 = torch.empty(B, N, Cc, device=dev, dtype=torch.float32)
+    dV0 = torch.empty(B, N, Cc, device=dev, dtype=torch.float32)
+    dgamma = torch.empty(Cc, device=dev, dtype=torch.float32)
+    dbeta = torch.empty(Cc, device=dev, dtype=torch.float32)
+    check(_lib.load().geoa3_edge_train_grad(
+        _p(g, torch.float32), _p(y, torch.float32), _p(U0, torch.float32), _p(V0, torch.float32), _p(arg, torch.int32),
+        _p(S1, torch.float32), _p(idx, torch.int64), _p(gamma, torch.float32), _p(stats, torch.float64), B, N, Cc, K,
+        _p(dU0), _p(dV0), _p(dgamma), _p(dbeta), _p(workspace), _stream()), "geoa3_edge_train_grad")
+    return dU0, dV0, dgamma, dbeta
+
+
 def knn_self_scratch(B: int, N: int, device) -> Tensor:
     """Scratch buffer of geoa3_knn_self for [B,3,N] clouds."""
     return torch.empty(int(_lib.load().geoa3_knn_self_scratch_bytes(B, N)), dtype=torch.uint8, device=device)

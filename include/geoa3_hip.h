@@ -864,6 +864,45 @@ int geoa3_wide_train_gather(const float* X, const float* coef, const int32_t* ar
 int geoa3_wide_train_scatter(const float* W, const float* coef, const int32_t* arg, int B, int N, int taps, float* dX,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The neighbour half of an EdgeConv layer (DGCNN) in TRAINING mode: max_k LeakyReLU_0.2(BatchNorm2d(W [x_j - x_i ; x_i])) with
+ * batch statistics, without the [B,2C,N,K] edge tensor or any [B,C,N,K] tensor, forward or backward.  With W = [W_a | W_b]
+ * the caller forms U0 = h W_a^T and V0 = h (W_b - W_a)^T ([B,N,C] point-major, unscaled); edge (i, s), j = idx[b,i,s], has the
+ * pre-BatchNorm value z = U0[j] + V0[i], and M = B N K.
+ * Limits: N K < 2^31 - 256, B <= 65535 (GEOA3_ENOSUPPORT otherwise); B N K >= 2 (GEOA3_EINVAL otherwise: one value has no
+ * batch variance, as torch refuses it).  Nothing is written when an entry refuses.  No floating-point atomics: sums are
+ * taken in an order that depends on the sizes and on idx only, repeated calls give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+/* bytes of `workspace` below (the per-tile partial sums and the destination lists of idx), 256-byte aligned; < 0 when the
+ * sizes are out of range */
+int64_t geoa3_edge_train_workspace_bytes(int B, int N, int C, int K);
+/* Forward.  gamma, beta [C], idx int64 [B,N,K] ->
+ *   arg[b,i,c] (int32 [B,N,C]) = the first maximum of U0[b, idx[b,i,.], c] where gamma[c] > 0, the first minimum where
+ *                gamma[c] < 0, slot 0 where gamma[c] == 0 (the float32 values are compared: ties go to the lower slot);
+ *   S1[b,i,c]  ([B,N,C])       = sum_s U0[b, idx[b,i,s], c], the sequential float32 sum from +0.0;
+ *   mean, var [C]              = the mean and the BIASED variance of z over the M edges, accumulated in double from the exact
+ *                value of u + v in a fixed order, rounded once;  stats (double [3][C]) = mean | var | 1 / sqrt(var + eps),
+ *                unrounded: what geoa3_edge_train_grad takes;
+ *   y[b,c,i]   ([B,C,N])       = lrelu(gamma r (U0[b,idx[b,i,arg],c] + V0[b,i,c] - mean) + beta), lrelu(a) = a > 0 ? a : 0.2 a,
+ *                formed in double, rounded once.
+ * An index outside [0,N) is never dereferenced; it makes EVERY y, mean, var of the call NaN (arg: its first such slot).
+ * A non-finite U0 / V0 value makes mean, var and y of its channel NaN. */
+int geoa3_edge_train_forward(const float* U0, const float* V0, const int64_t* idx, const float* gamma, const float* beta,
+                             float eps, int B, int N, int C, int K, float* y, int32_t* arg, float* S1, float* mean,
+                             float* var, double* stats, void* workspace, void* stream);
+/* Backward.  g, y [B,C,N]; U0, V0, arg, S1, idx, gamma, stats as above.  With g' = y > 0 ? g : fl(0.2f g) and
+ * zhat = (z - mean) r:
+ *   dbeta [C]  = sum_{b,i} g',   dgamma [C] = sum_{b,i} g' zhat_sel     (double partial sums in a fixed order, rounded once)
+ *   dV0[b,i,c] = gamma r ( g' - K dbeta / M - (dgamma / M) r ( S1 + K V0 - K mean ) )
+ *   dU0[b,j,c] = gamma r ( sum_{(i,s)->j, s == arg[i]} g'[i] - indeg(j) dbeta / M
+ *                          - (dgamma / M) r ( indeg(j) (U0[j] - mean) + sum_{(i,s)->j} V0[i] ) )
+ * where (i,s)->j runs over the entries of idx[b] equal to j, with multiplicity, in ascending (i, s) order; both sums are
+ * sequential float32 sums from +0.0, the rest is formed in double and rounded once.  An index outside [0,N) gives no term.
+ * dU0, dV0 [B,N,C], every element written. */
+int geoa3_edge_train_grad(const float* g, const float* y, const float* U0, const float* V0, const int32_t* arg,
+                          const float* S1, const int64_t* idx, const float* gamma, const double* stats, int B, int N, int C,
+                          int K, float* dU0, float* dV0, float* dgamma, float* dbeta, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

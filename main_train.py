@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Train the PointNet victim -- the job of the reference's main_train.py, with its flags, defaults, loop and files:
+"""Train the PointNet victim, or the DGCNN one -- the job of the reference's main_train.py, with its flags, defaults, loop and files:
 
     python main_train.py --datadir /data/modelnet40_normal_resampled --is_aug_data
     python main_train.py --mesh_dir ModelNet40 --shape_names_file modelnet40_shape_names.txt --is_aug_data
     python main_train.py --synthetic -c 5 --npoint 256 -b 16 --epochs 3
+    python main_train.py --arch DGCNN --edge_train fused --datadir /data/modelnet40_normal_resampled --is_aug_data
 
 Loop (main_train.py:188-347): label-smoothing loss at 0.2 + 0.001 ||T T^T - I||^2 / 2 on the feature transform, Adam with
 per-parameter weight decay, lr 0.7^(epoch // 20) floored at 1e-5, the BatchNorm momentum schedule, the [0,2,1] axis swap of
@@ -18,6 +19,13 @@ layer of geoa3_amd/pointnet_train.py (default: torch, the plain composition, the
 Extensions: --mesh_dir / --shape_names_file / --surface_samples (ROOT/<class>/train|test/*.off|*.obj through the reader and
 surface sampler of Provider/gen_data_mat.py), --synthetic / --synthetic_instances (seeded CAD-like clouds, the label is
 the kind: 5 classes), --wide_train, --quiet.
+
+--arch DGCNN trains only together with --edge_train fused | torch (how a training step runs the four EdgeConv layers: the
+fused HIP layer of geoa3_amd/dgcnn_train.py -- at B 32, N 1024 a step peaks at 0.95 GB against 5.3 GB and takes 11.2 against
+32.4 ms: DESIGN.md 8e -- or the plain torch composition);
+without it the arch is refused as before.  The loop is the one above with two differences: the loss is the smoothed-label
+loss alone (DGCNN has no feature transform), and the BatchNorm momentum stays the module's own (--bn_momentum does not
+apply).  --dgcnn_k, --emb_dims, --dropout are the public model's k, emb_dims and dropout.  Files: Pretrained/DGCNN/<npoint>/.
 """
 from __future__ import annotations
 
@@ -52,7 +60,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--epochs", default=250, type=int, metavar="N", help="number of total epochs to run")
     p.add_argument("--lr", default=0.001, type=float, metavar="LR", help="initial learning rate")
     p.add_argument("--decay-epochs", default=20, type=int, metavar="N", help="number of epochs to decay")
-    p.add_argument("--bn_momentum", default=0.5, type=float, metavar="BN", help="initial bn momentum")
+    p.add_argument("--bn_momentum", default=0.5, type=float, metavar="BN", help="initial bn momentum (PointNet; does not apply to DGCNN, whose BatchNorm momentum stays the module's own)")
     p.add_argument("--wd", default=0.0001, type=float, metavar="W", help="weight decay (default: 1e-4)")
     p.add_argument("--resume", default="", type=str, metavar="PATH", help="path to latest checkpoint (default: none)")
     p.add_argument("--is_use_tb", dest="is_use_tb", action="store_true", default=False, help="Using Tensorboard")
@@ -69,6 +77,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--wide_train", default="torch", choices=["fused", "torch"],
                    help="the 1024-wide layers of a training step: the fused HIP layer (a third of the peak memory), or the "
                         "plain torch composition (the faster step at B 32, N 1024: DESIGN.md 8d)")
+    p.add_argument("--edge_train", default=None, choices=["fused", "torch"],
+                   help="--arch DGCNN: the EdgeConv layers of a training step: the fused HIP layer (no [B,C,N,k] tensor is "
+                        "written), or the plain torch composition.  Required to train DGCNN; both values are explicit")
+    p.add_argument("--dgcnn_k", default=20, type=int, help="--arch DGCNN: neighbours per point")
+    p.add_argument("--emb_dims", default=1024, type=int, help="--arch DGCNN: width of the embedding (conv5)")
+    p.add_argument("--dropout", default=0.5, type=float, help="--arch DGCNN: dropout of the head")
     p.add_argument("--quiet", action="store_true", default=False)
     return p
 
@@ -76,16 +90,17 @@ def build_parser() -> argparse.ArgumentParser:
 REFUSED_ARCHS = {
     "PointNetPP": "--arch PointNetPP cannot be trained here: the training-mode forward of geoa3_amd.pointnet2 raises "
                   "(its set-abstraction kernels are eval-mode only); only --arch PointNet is trained",
-    "DGCNN": "--arch DGCNN cannot be trained here: the training-mode forward of geoa3_amd.dgcnn raises (its EdgeConv kernels "
-             "fold BatchNorm's running statistics); only --arch PointNet is trained",
+    "DGCNN": "--arch DGCNN is not trained without --edge_train fused | torch: by default the training-mode forward of "
+             "geoa3_amd.dgcnn raises (its eval-mode EdgeConv kernels fold BatchNorm's running statistics); the flag selects "
+             "the train-mode EdgeConv layer of geoa3_amd/dgcnn_train.py",
 }
 
 
 def check_supported(cfg) -> None:
     """The refusals, by name, before anything is read or written."""
-    if cfg.arch in REFUSED_ARCHS:
+    if cfg.arch in REFUSED_ARCHS and not (cfg.arch == "DGCNN" and getattr(cfg, "edge_train", None) is not None):
         raise NotImplementedError(REFUSED_ARCHS[cfg.arch])
-    if cfg.arch != "PointNet":
+    if cfg.arch not in ("PointNet", "DGCNN"):
         raise AssertionError("Not support such arch.")
     if cfg.mGPU > 1:
         raise NotImplementedError("-g / --mGPU %d cannot be honoured: training runs on one GPU (the fused wide layer takes "
@@ -226,8 +241,14 @@ def main(cfg):
     if int(max(trn_y.max(), tst_y.max())) >= cfg.classes:
         raise ValueError("the data holds label %d, the network has %d classes (-c)" % (int(max(trn_y.max(), tst_y.max())), cfg.classes))
 
-    net = PointNet(cfg.classes).to(device)
-    net.wide_train = cfg.wide_train
+    dgcnn = cfg.arch == "DGCNN"
+    if dgcnn:
+        from geoa3_amd.dgcnn import DGCNN
+        net = DGCNN(k=cfg.dgcnn_k, emb_dims=cfg.emb_dims, dropout=cfg.dropout, output_channels=cfg.classes).to(device)
+        net.edge_train = cfg.edge_train
+    else:
+        net = PointNet(cfg.classes).to(device)
+        net.wide_train = cfg.wide_train
     criterion = SmoothedLabelLoss(cfg.classes)
     params = [{"params": [v], "lr": cfg.lr, "weight_decay": cfg.wd} for v in net.parameters() if v.requires_grad]
     optimizer = torch.optim.Adam(params)
@@ -260,8 +281,12 @@ def main(cfg):
             if cfg.is_aug_data:
                 points = augment_batch(points, gen)
             optimizer.zero_grad()
-            output, transform = net(to_network_frame(points))
-            loss = criterion(output, target) + transform_penalty(transform) * 0.001
+            if dgcnn:
+                output = net(to_network_frame(points))
+                loss = criterion(output, target)
+            else:
+                output, transform = net(to_network_frame(points))
+                loss = criterion(output, target) + transform_penalty(transform) * 0.001
             loss.backward()
             optimizer.step()
             loss_sum += loss.detach().double() * idx.numel()
@@ -271,7 +296,8 @@ def main(cfg):
         seen = trn_x.shape[0] - (1 if trn_x.shape[0] % B == 1 else 0)
         trn_loss, trn_acc = float(loss_sum) / seen, 100.0 * float(hit_sum) / seen
         adjust_learning_rate(optimizer, epoch, cfg.lr)
-        net.adjust_bn_momentum(epoch, cfg.bn_momentum)
+        if not dgcnn:
+            net.adjust_bn_momentum(epoch, cfg.bn_momentum)
         with open(os.path.join(modeldir, "result.txt"), "at") as f:
             f.write("epoch[{:3d}] train-acc: {:.3f}".format(epoch, trn_acc))
 
